@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the BC7 hot path (BASELINE.json).  Rank 0 prints ONE short JSON line (< 4 KB: the contract's fields, `roofline`,
-`cpu_baseline`, one entry per other BASELINE config) as the last line of stdout and writes every leg in full to bench_detail.json.
+and with --full `cpu_baseline` and one entry per other BASELINE config) as the last line of stdout and writes every leg in full
+to bench_detail.json.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
             (`python bench.py --gpus N` without a launcher starts exactly that itself)
 
+A plain run sets up, warms up, times the K steps and prints the line: the headline and the `roofline` of the timed launches
+(HIP events of the timed steps, no runs of their own).  --full adds every other leg below (CPU baselines, other configs and
+content, sustained rate, reference comparisons).  --dump-outputs DIR writes what the last timed step returned to
+DIR/bc7_blocks.npy (float32, one value per output byte, a fixed sample of rows beyond DUMP_LIMIT_BYTES), so that two builds
+can be compared output for output on the same seeded input.
+
 N = 1  -- BASELINE configs[1]: EncodeBC7, BC7EncodingPlan() + Options(), 4096x4096 SplitMix64 random RGBA (seed 2),
-          PixelBlocks resident in HBM.  A step = one encode of the image.  Besides the headline the line carries
-          `roofline` (HIP events on the launch stream), `sustained` (>= 3 s of back-to-back encodes + the shader clock),
+          PixelBlocks resident in HBM.  A step = one encode of the image.  With --full the line also carries
+          `sustained` (>= 3 s of back-to-back encodes + the shader clock),
           `cpu_baseline` (the real reference from oracle/_ref on this box's host cores, 1 thread and all threads, driven by
           std::thread, and the count of GPU != CPU blocks), `configs` (one measurement per other BASELINE config: 1, 2b, 3,
           4, 5a, 5b), `content_families` (the same kernel on eight kinds of content) and `host_path` (the host-pointer
@@ -55,8 +62,13 @@ def parse_args(argv=None):
                     help="auto: config2 (4096^2, BASELINE configs[1]) on one GPU, config5 (one 16384^2 image, block-row sharded) on several")
     ap.add_argument("--size", type=int, default=0, help="image edge in pixels (default: the workload's)")
     ap.add_argument("--opaque", action="store_true", help="variant 2b: alpha forced to 255 (modes 0-3 run)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip every CPU leg")
-    ap.add_argument("--no-extra", action="store_true", help="headline only (profiling runs): no sustained / configs / families / host path")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baselines, the other BASELINE configs, content families, sustained rate, two streams, "
+                         "exhaustive search, host path, drop-in calls (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the packed blocks of the last timed step to DIR/bc7_blocks.npy (float32, <= DUMP_LIMIT_BYTES)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip every CPU leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no sustained / configs / families / host path")
     ap.add_argument("--exhaustive", action="store_true",
                     help="evaluate every candidate like the reference (default: exact branch-and-bound, same output)")
     ap.add_argument("--dry-run", action="store_true",
@@ -96,6 +108,22 @@ def golden_rcp(h):
 
 def sha256(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+DUMP_LIMIT_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, blocks):
+    """--dump-outputs: the (n, 16) uint8 packed blocks a caller of the timed path receives, as DIR/bc7_blocks.npy in float32 (one
+    value per byte, exact).  An output larger than DUMP_LIMIT_BYTES as float32 is cut to a sample of rows drawn with a fixed seed
+    and kept in block order, the same rows for every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    n, width = blocks.shape
+    rows = DUMP_LIMIT_BYTES // (width * 4)
+    if n > rows:
+        blocks = blocks[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, rows, replace=False))]
+    np.save(os.path.join(dirname, "bc7_blocks.npy"), blocks.astype(np.float32))
 
 
 
@@ -376,6 +404,8 @@ def run_sharded(args):
     if rank == 0:
         last = full[(args.steps - 1) & 1] if args.steps > 0 else full[(args.warmup - 1) & 1]
         got = last.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got)
         digest = sha256(got)
         check = {"sha256": digest}
         if args.steps > 0:
@@ -431,7 +461,7 @@ def run_sharded(args):
                 result["roofline"] = roofline_block("bc7", nloc, k_ms, "cvttmi_bc7_kernel")
             result["roofline"]["note"] = "rank 0's shard (%d blocks) per launch; per-block counters of the 4096^2 profile of the same kernel" % nloc
             result["rank0_search_mblocks_s"] = nloc / k_ms / 1e3
-            if not args.no_cpu:
+            if args.full and not args.no_cpu:
                 # the CPU path on a bounded sample of rank 0's shard (the golden RCPPS table is in use on every rank)
                 opt_b = np.frombuffer(api.Options().tobytes(), np.uint8).copy()
                 plan_b = np.frombuffer(api.BC7EncodingPlan().tobytes(), np.uint8).copy()
@@ -689,6 +719,8 @@ def run_single(args):
     mblocks = nblk * args.steps / elapsed / 1e6
     achieved = ALGO_BYTES["bc7"] * nblk / (k_ms * 1e-3) / 1e9
     out_host = d_out.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_host)
 
     result = {
         "metric": "bc7_encode_default_plan_throughput",
@@ -734,7 +766,7 @@ def run_single(args):
                                 "peak": VALU_PEAK, "frac": result["roofline"]["frac"], "avg_waves_per_simd": pmc.get("avg_waves_per_simd"),
                                 "source": pmc["source"]}
 
-    if not args.no_extra and not args.exhaustive:
+    if args.full and not args.no_extra and not args.exhaustive:
         # ---- sustained rate: >= 3 s of back-to-back encodes, shader clock sampled while they run
         target_s = 3.0
         per = max(1, int(0.25 / max(1e-4, k_ms * 1e-3)))
@@ -800,12 +832,12 @@ def run_single(args):
                                        "identical_output": bool((d_out.cpu().numpy() == out_host).all())}
         ctx.set_exhaustive(False)
 
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline("bc7", blocks, out_host, opt_b, plan_b, rcp, budget_one=3.0, budget_all=8.0)
         result["cpu_baseline"]["host"] = host_info()
         result["bit_exact_vs_cpu"] = result["cpu_baseline"]["gpu_mismatching_blocks"] == 0
 
-    if not args.no_extra and not args.exhaustive and not args.opaque and size == 4096:
+    if args.full and not args.no_extra and not args.exhaustive and not args.opaque and size == 4096:
         # (the host-path leg first: after the 16384^2 legs have churned a few GB of host memory it measures 30 % lower)
         hp = host_path_leg(torch, api, ctx, blocks, out_host, opt, plan)
         if hp:

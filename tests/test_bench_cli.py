@@ -76,6 +76,48 @@ def test_three_ranks_ragged_shards_dry_run():
     assert r["output_check"]["matches_single_process"] is True
 
 
+def test_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs DIR: the blocks of the last timed step as float32 DIR/bc7_blocks.npy, byte for byte what the stand-in
+    computes on the whole image, and the same file for two runs with the same arguments"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import torch
+    from convectionkernels_amd import synth
+    want = bench.stand_in_encoder(torch.from_numpy(synth.tile_blocks(synth.image_rgba8(5, 256, 256)))).numpy()
+    for k in range(2):
+        d = tmp_path / str(k)
+        p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dry-run", "--size", "256", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert r["steps"] == 2 and "ms_per_step" in r
+        got = np.load(d / "bc7_blocks.npy")
+        assert got.dtype == np.float32 and got.shape == (4096, 16)
+        assert (got == want).all()
+
+
+def test_dump_outputs_samples_rows_beyond_the_limit(tmp_path, monkeypatch):
+    """an output larger than DUMP_LIMIT_BYTES as float32 is cut to a fixed, seeded sample of whole rows in block order"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * 16 * 4)
+    blocks = np.arange(1000 * 16, dtype=np.uint32).reshape(1000, 16)
+    blocks = (blocks % 251).astype(np.uint8)
+    blocks[:, 0] = np.arange(1000) % 256
+    blocks[:, 1] = np.arange(1000) // 256
+    dumps = []
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), blocks)
+        dumps.append(np.load(tmp_path / str(k) / "bc7_blocks.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (100, 16) and a.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert (a == dumps[1]).all()
+    idx = (a[:, 0] + 256 * a[:, 1]).astype(np.int64)
+    assert (np.diff(idx) > 0).all() and (a == blocks[idx]).all()
+
+
 def test_roofline_arithmetic_on_synthetic_counters():
     """bench.roofline_block: VALU issue fraction, HBM view and traffic ratio from given counters (no profile, no GPU)"""
     sys.path.insert(0, ROOT)

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 STEPS="--steps 20 --warmup 5"
-python bench.py $STEPS "$@" > $OUT/bench.json 2> $OUT/bench.err
+python bench.py $STEPS --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bc7 -- python bench.py $STEPS --no-cpu --no-extra "$@" > $OUT/trace.log 2>&1
 # counters in their own runs (never together with --stats or a trace domain other than the kernel trace); the summary takes
 # the LAST dispatch of every kernel -- 24 launches after start-up, clocks and caches warm -- and the mean over the timed ones
