@@ -4435,17 +4435,14 @@ extern "C" hipError_t cvttmi_launch_bc7(const void *d_blocks, void *d_out, const
         return hipSuccess;
     const bool fast = (args->flags & CVTTMI_FLAG_BC7_FAST_INDEXING) != 0;
     const bool pt = (args->flags & CVTTMI_FLAG_BC7_RESPECT_PUNCHTHROUGH) != 0;
-    // developer knob: extra (unused) dynamic LDS per workgroup, to pin the number of resident waves per SIMD in experiments
-    static const unsigned ldsPad = getenv("CVTTMI_BC7_LDS_PAD") ? (unsigned)atoi(getenv("CVTTMI_BC7_LDS_PAD")) : 0u;
-#define CVTT_LAUNCH(F, P, H, GRID) hipLaunchKernelGGL((cvttmi_bc7_kernel<F, P, H>), dim3(GRID), dim3(64), (H) ? 0u : ldsPad, stream, (const uint8_t *)d_blocks, (uint8_t *)d_out, *args, d_tables, d_plan)
-    if (pt)
+#define CVTT_LAUNCH(F, P, H, GRID) hipLaunchKernelGGL((cvttmi_bc7_kernel<F, P, H>), dim3(GRID), dim3(64), 0, stream, (const uint8_t *)d_blocks, (uint8_t *)d_out, *args, d_tables, d_plan)
+    if (pt) // no hand-over: this kernel does not clear the next encode's counter, so the shim gives it no slots
     {
         if (fast) CVTT_LAUNCH(true, true, false, waves); else CVTT_LAUNCH(false, true, false, waves);
         return hipGetLastError();
     }
-    const bool split = args->hardCap != 0; // (the hand-over counter is zero: the previous encode's first launch cleared it, the context's creation the first two)
     if (fast) CVTT_LAUNCH(true, false, false, waves); else CVTT_LAUNCH(false, false, false, waves);
-    if (split)
+    if (args->hardCap != 0) // (the counter is zero: the previous encode's first launch cleared it, the context's creation the first two)
     {
         // a fixed grid that walks the items (kHardWaves per recorded block): one resident generation at most
         const uint32_t hardItems = args->hardCap * (uint32_t)kHardWaves;

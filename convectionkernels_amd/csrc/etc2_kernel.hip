@@ -2694,8 +2694,7 @@ __global__ __launch_bounds__(64) void cvttmi_eac_alpha_kernel(const uint8_t *__r
 
 // Launches of at most this many blocks use the sixteen-lanes-per-block form of the EAC search: the chip is not full there
 // (256 CUs x 4 SIMDs x 4 waves x 64 lanes = 262 144 blocks resident in the one-lane form), so latency is what counts.
-// CVTTMI_EAC_SPREAD_MAX in the environment overrides it (developer knob for A/B runs).
-static const uint32_t kEacSpreadMax = getenv("CVTTMI_EAC_SPREAD_MAX") ? (uint32_t)atol(getenv("CVTTMI_EAC_SPREAD_MAX")) : 65536u;
+static const uint32_t kEacSpreadMax = 65536u;
 
 extern "C" hipError_t cvttmi_launch_etc2(const void *d_blocks, void *d_out, const CvttEtcArgs *args,
                                          const CvttDeviceTables *d_tables, int mode, hipStream_t stream)

@@ -365,8 +365,8 @@ int cvttmi_dropin_set_devices(const int *devices, int numDevices);
  * arithmetic contract behind bit-exactness (reference ParallelMath.h:261-323, 959-965). */
 int cvttmi_selftest_arith(cvttmi_context *ctx, uint64_t count, uint64_t seed, uint64_t *divMismatches, uint64_t *sqrtMismatches);
 
-/* Time (ms, HIP events on the launch stream) and launch count of the kernels of the most
- * recent *_device call sequence since cvttmi_timing_reset(); used by bench.py's roofline. */
+/* Time (ms, HIP events on the launch stream) and count of the encode and decode calls since timing
+ * was last enabled: each *_device call counts once, a host-pointer call once per launch of its pipeline. */
 int cvttmi_timing_enable(cvttmi_context *ctx, int enable);
 int cvttmi_timing_read(cvttmi_context *ctx, double *totalMs, uint64_t *launches);
 

@@ -256,6 +256,42 @@ def test_second_launch_hand_over_is_invisible(gpu_ctx, oracle_lib, monkeypatch):
         bad = _diff(ctx.encode_bc7(blocks, opt, plan), exp)
         assert bad.size == 0, "%s: blocks %s differ" % (env, bad[:8])
 
+    # A punch-through encode between two encodes with a hand-over, on one context.  The two hand-over counters alternate,
+    # each encode's first kernel clearing the next one's; the punch-through kernel clears none, so it gets no slots, and
+    # the third encode must not start on the first one's records.  (Equal block counts: stale records would still point
+    # inside the buffers.)
+    import ctypes
+    for k in ("CVTTMI_BC7_HARD_MIN", "CVTTMI_BC7_HARD_CAP", "CVTTMI_BC7_HARD_DIV"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("CVTTMI_BC7_HARD_CAP", "4096")
+    monkeypatch.setenv("CVTTMI_BC7_HARD_MIN", "2")
+    ctx = api.Context(0)
+    ctx.set_rcp_table(rcp)
+    lib = api.load_library()
+    lib.cvttmi_bc7_hard_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+
+    def hard_stats():
+        n, slots = ctypes.c_uint32(), ctypes.c_uint32()
+        assert lib.cvttmi_bc7_hard_stats(ctx._h, ctypes.byref(n), ctypes.byref(slots)) == 0
+        return n.value, slots.value
+
+    opt_pt = api.Options(flags=api.Flags.Default | api.Flags.BC7_RespectPunchThrough)
+    exp_pt = oracle_lib.encode_bc7(blocks, np.frombuffer(opt_pt.tobytes(), np.uint8).copy(),
+                                   np.frombuffer(plan.tobytes(), np.uint8).copy(), rcp, threads=8)
+    other = np.concatenate([content.mixed_ldr_blocks(778, 40), content.config_blocks(10, 256, 256)])
+    assert other.shape == blocks.shape
+    exp_other = oracle_lib.encode_bc7(other, np.frombuffer(opt.tobytes(), np.uint8).copy(),
+                                      np.frombuffer(plan.tobytes(), np.uint8).copy(), rcp, threads=8)
+    bad = _diff(ctx.encode_bc7(blocks, opt, plan), exp)
+    assert bad.size == 0, "first encode: blocks %s differ" % bad[:8]
+    handed, slots = hard_stats()
+    assert slots == 4096 and handed > 0, (handed, slots)
+    bad = _diff(ctx.encode_bc7(blocks, opt_pt, plan), exp_pt)
+    assert bad.size == 0, "punch-through encode: blocks %s differ" % bad[:8]
+    assert hard_stats() == (0, 0)
+    bad = _diff(ctx.encode_bc7(other, opt, plan), exp_other)
+    assert bad.size == 0, "third encode: blocks %s differ" % bad[:8]
+
 
 def test_config2_full_size_hash(gpu_ctx):
     """BASELINE config 2: 4096x4096 random RGBA, seed 2 (1,048,576 blocks) -- SHA-256 of the
