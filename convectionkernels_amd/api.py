@@ -301,6 +301,17 @@ def load_library():
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     lib.cvttmi_decode_bc6h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    lib.cvttmi_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.cvttmi_decode.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    lib.cvttmi_measure_error_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.cvttmi_measure_error.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+    lib.cvttmi_measure_image_error_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p]
+    lib.cvttmi_psnr.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.cvttmi_psnr.restype = ctypes.c_double
     lib.cvttmi_selftest_arith.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64)]
     lib.cvttmi_bc7_plan_from_quality.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -337,6 +348,54 @@ def load_library():
         lib.cvttmi_dropin_set_devices.argtypes = [ctypes.c_void_p, ctypes.c_int]
     _lib = lib
     return lib
+
+
+# Decode / measure formats (include/cvtt_mi355x.h CVTTMI_FMT_*): name -> (id, packed bytes, decoded bytes, channel mask).
+# Names as encode_image and container.FORMATS use them, plus "r11u" / "r11s" (EAC R11 from PixelBlockScalarS16).
+TEXTURE_FORMATS = {
+    "bc7": (0, 16, 64, 0xF), "bc1": (1, 8, 64, 0xF), "bc6hu": (2, 16, 128, 0x7), "bc6hs": (3, 16, 128, 0x7),
+    "etc2": (4, 8, 64, 0x7), "etc2rgb": (4, 8, 64, 0x7), "etc2rgba": (5, 16, 64, 0xF), "bc2": (6, 16, 64, 0xF),
+    "bc3": (7, 16, 64, 0xF), "bc4u": (8, 8, 64, 0x1), "bc4s": (9, 8, 64, 0x1), "bc5u": (10, 16, 64, 0x3),
+    "bc5s": (11, 16, 64, 0x3), "etc1": (12, 8, 64, 0x7), "etc2punchthrough": (13, 8, 64, 0xF), "eac": (14, 8, 64, 0x8),
+    "r11u": (15, 8, 32, 0x1), "r11s": (16, 8, 32, 0x1),
+}
+
+
+class ErrorTotals(ctypes.Structure):
+    """byte image of cvttmi_error_totals"""
+    _fields_ = [("sse", ctypes.c_uint64 * 4), ("sseHdr", ctypes.c_double * 4), ("texels", ctypes.c_uint64),
+                ("channelMask", ctypes.c_uint32), ("format", ctypes.c_int32)]
+
+
+def psnr_of_totals(totals, channel_mask=0):
+    """cvttmi_psnr: dB over the channels of channel_mask (0 = the format's)"""
+    return float(load_library().cvttmi_psnr(ctypes.addressof(totals), int(channel_mask)))
+
+
+class ErrorReport:
+    """Result of Context.measure_error / measure_image: per-channel SSE and MSE (R, G, B, A; channels the format does not
+    store are 0 and not in `channels`), the texels counted per channel, psnr(), and the per-block values when asked for."""
+    _CH = {"r": 1, "g": 2, "b": 4, "a": 8}
+
+    def __init__(self, fmt, totals, per_block=None):
+        self.format = fmt
+        self.totals = totals
+        self.channel_mask = int(totals.channelMask)
+        self.texels = int(totals.texels)
+        hdr = fmt in ("bc6hu", "bc6hs")
+        self.sse = [float(totals.sseHdr[c]) if hdr else int(totals.sse[c]) for c in range(4)]
+        self.mse = [(s / self.texels if self.texels else float("nan")) if (self.channel_mask >> c) & 1 else 0.0
+                    for c, s in enumerate(self.sse)]
+        self.channels = "".join(ch for ch, bit in self._CH.items() if self.channel_mask & bit)
+        self.per_block = per_block
+
+    def psnr(self, channels=None):
+        """dB over `channels` ("rgb", "a", a mask, None = every channel the format stores); NaN for BC6H"""
+        mask = channels if isinstance(channels, int) else sum(self._CH[c] for c in (channels or "").lower())
+        return psnr_of_totals(self.totals, mask)
+
+    def __repr__(self):
+        return "ErrorReport(%s, mse=%s, texels=%d, psnr=%.3f)" % (self.format, self.mse, self.texels, self.psnr())
 
 
 def library_source_sha256():
@@ -687,6 +746,115 @@ class Context:
         d = self.decode_bc7(packed).to(torch.float32) - blocks.reshape(-1, 16, 4).to(torch.float32)
         mse = float((d * d).mean().item())
         return float("inf") if mse == 0.0 else 10.0 * float(np.log10(255.0 * 255.0 / mse))
+
+    # -- every format: decode, and the encoding error in one pass (include/cvtt_mi355x.h) --
+    @staticmethod
+    def _texture_format(fmt):
+        if fmt not in TEXTURE_FORMATS:
+            raise CvttError("unknown format %r" % (fmt,))
+        return TEXTURE_FORMATS[fmt]
+
+    @staticmethod
+    def _decoded_layout(fmt, n):
+        """(shape, numpy dtype) of the decoded blocks: what the format's encoder reads"""
+        if fmt in ("bc6hu", "bc6hs"):
+            return (n, 16, 4), np.int16
+        if fmt in ("r11u", "r11s"):
+            return (n, 16), np.int16
+        return (n, 16, 4), (np.int8 if fmt in ("bc4s", "bc5s") else np.uint8)
+
+    def decode(self, fmt, packed, stream=None):
+        """(N, bytes) packed blocks of `fmt` (numpy or CUDA tensor) -> the layout its encoder reads: (N,16,4) uint8
+        (BC4S / BC5S int8; BC6H int16 half bits), R11 (N,16) int16"""
+        fid, bpb, _, _ = self._texture_format(fmt)
+        if isinstance(packed, np.ndarray):
+            b = np.ascontiguousarray(packed, np.uint8)
+            n = b.size // bpb
+            if b.size % bpb or n % NumParallelBlocks:
+                raise CvttError("packed must hold a multiple of 8 %d-byte blocks" % bpb)
+            shape, dt = self._decoded_layout(fmt, n)
+            res = np.empty(shape, dt)
+            with self._host_lock:
+                self._check(self._lib.cvttmi_decode(self._h, fid, res.ctypes.data, b.ctypes.data, n), "decode(%s)" % fmt)
+            return res
+        import torch
+        b = self._device_in(packed, "packed")
+        nbytes = b.numel() * b.element_size()
+        n = nbytes // bpb
+        if nbytes % bpb or n % NumParallelBlocks:
+            raise CvttError("packed must hold a multiple of 8 %d-byte blocks" % bpb)
+        shape, dt = self._decoded_layout(fmt, n)
+        res = torch.empty(shape, dtype={np.int16: torch.int16, np.int8: torch.int8, np.uint8: torch.uint8}[dt], device=b.device)
+        stream = self._stream(stream, b.device)
+        self._check(self._lib.cvttmi_decode_device(self._h, fid, res.data_ptr(), b.data_ptr(), n, ctypes.c_void_p(stream)),
+                    "decode(%s)" % fmt)
+        return res
+
+    def measure_error(self, fmt, blocks, packed, per_block=False, stream=None):
+        """Error of the packed blocks of `fmt` against their source `blocks` (the encoder's input layout: PixelBlockU8,
+        PixelBlockS8 for BC4S / BC5S, PixelBlockF16 for BC6H, PixelBlockScalarS16 for R11), decoded in registers on the
+        device.  numpy inputs go through the host entry, CUDA tensors through the device entry on `stream`.
+        per_block: also return each block's summed squared error (uint32; float32 for BC6H) as ErrorReport.per_block."""
+        fid, bpb, tex, _ = self._texture_format(fmt)
+        hdr = fmt in ("bc6hu", "bc6hs")
+        if isinstance(packed, np.ndarray):
+            b = np.ascontiguousarray(packed, np.uint8)
+            s = np.ascontiguousarray(blocks)
+            n = b.size // bpb
+            if b.size % bpb or n % NumParallelBlocks or s.nbytes != n * tex:
+                raise CvttError("packed must hold a multiple of 8 %d-byte blocks and blocks exactly as many %d-byte source blocks"
+                                % (bpb, tex))
+            totals = ErrorTotals()
+            pb = np.empty(n, np.float32 if hdr else np.uint32) if per_block else None
+            with self._host_lock:
+                self._check(self._lib.cvttmi_measure_error(self._h, fid, b.ctypes.data, s.ctypes.data, n,
+                                                           pb.ctypes.data if per_block else None, ctypes.addressof(totals)),
+                            "measure_error(%s)" % fmt)
+            return ErrorReport(fmt, totals, pb)
+        import torch
+        b = self._device_in(packed, "packed")
+        s = self._device_in(blocks, "blocks")
+        nbytes = b.numel() * b.element_size()
+        n = nbytes // bpb
+        if nbytes % bpb or n % NumParallelBlocks or s.numel() * s.element_size() != n * tex:
+            raise CvttError("packed must hold a multiple of 8 %d-byte blocks and blocks exactly as many %d-byte source blocks"
+                            % (bpb, tex))
+        return self._measure_device(fmt, n, per_block, stream, b.device, lambda pb, tot, st: self._lib.cvttmi_measure_error_device(
+            self._h, fid, b.data_ptr(), s.data_ptr(), n, pb, tot, st))
+
+    def _measure_device(self, fmt, n, per_block, stream, device, call):
+        import torch
+        hdr = fmt in ("bc6hu", "bc6hs")
+        # (per-block values are uint32 below 2^31 -- at most 16 x 2047^2 -- so an int32 tensor holds them; the totals need no
+        # initial value: the call writes all of them, on `stream`)
+        tot = torch.empty(ctypes.sizeof(ErrorTotals), dtype=torch.uint8, device=device)
+        pb = torch.empty(n, dtype=torch.float32 if hdr else torch.int32, device=device) if per_block else None
+        stream = self._stream(stream, device)
+        self._check(call(pb.data_ptr() if per_block else None, tot.data_ptr(), ctypes.c_void_p(stream)), "measure(%s)" % fmt)
+        torch.cuda.synchronize(device)
+        totals = ErrorTotals.from_buffer_copy(tot.cpu().numpy().tobytes())
+        return ErrorReport(fmt, totals, pb)
+
+    def measure_image(self, fmt, image, packed, per_block=False, stream=None):
+        """Error of `packed` (what encode_image(fmt, image) returns: ceil(W/4) x ceil(H/4) blocks, row-major) against the
+        (H,W,4) CUDA image it was encoded from (uint8 RGBA8; a 2-byte dtype for BC6H's RGBA16F); texels outside W x H count
+        nowhere.  Every format but R11."""
+        import torch
+        fid, bpb, _, _ = self._texture_format(fmt)
+        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 3 and image.shape[2] == 4):
+            raise CvttError("image must be a CUDA tensor of shape (H, W, 4)")
+        if image.device.index != self.device:
+            raise CvttError("image lives on cuda:%d but this context was created for cuda:%d" % (image.device.index, self.device))
+        if image.stride(2) != 1 or image.stride(1) != 4:
+            image = image.contiguous()
+        h, w = int(image.shape[0]), int(image.shape[1])
+        esz = image.element_size()
+        b = self._device_in(packed, "packed")
+        n = ((w + 3) // 4) * ((h + 3) // 4)
+        if b.numel() * b.element_size() != n * bpb:
+            raise CvttError("packed must hold the %d blocks of a %dx%d image" % (n, w, h))
+        return self._measure_device(fmt, n, per_block, stream, b.device, lambda pb, tot, st: self._lib.cvttmi_measure_image_error_device(
+            self._h, fid, b.data_ptr(), image.data_ptr(), w, h, image.stride(0) * esz, 0 if esz == 1 else 1, pb, tot, st))
 
     def selftest_arith(self, count=1 << 22, seed=1):
         """(divide mismatches, sqrt mismatches) of the device against the host's IEEE results"""

@@ -5,6 +5,9 @@
 // device (decode + PSNR) independently of bit-exactness.  Blocks with a reserved mode decode to
 // zeros (BC7) / zeros with alpha 1.0 (BC6H), like the reference.
 #include "cvtt_kernel_common.h"
+#include <hip/hip_fp16.h>
+#include <type_traits>
+#include "texture_formats.h"
 
 namespace
 {
@@ -38,15 +41,10 @@ __device__ __forceinline__ int bc7Weight(int indexBits, int index)
     return (rcp * index + 256) >> 9;
 }
 
-__global__ void cvttmi_decode_bc7_kernel(const uint8_t *__restrict__ bc, uint8_t *__restrict__ out, u32 numBlocks,
-                                         const CvttDeviceTables *__restrict__ T)
+// one BC7 block -> 16 RGBA8 texels (R in the low byte)
+__device__ __forceinline__ void bc7Block(const uint4 raw, const CvttDeviceTables *__restrict__ T, u32 pixels[16])
 {
-    const u32 block = blockIdx.x * blockDim.x + threadIdx.x;
-    if (block >= numBlocks)
-        return;
-    const uint4 raw = *reinterpret_cast<const uint4 *>(bc + (size_t)block * 16u);
     BitReader br = {((u64)raw.y << 32) | raw.x, ((u64)raw.w << 32) | raw.z, 0};
-    uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)block * 64u);
 
     int mode = 8;
     for (int i = 0; i < 8; i++)
@@ -57,8 +55,8 @@ __global__ void cvttmi_decode_bc7_kernel(const uint8_t *__restrict__ bc, uint8_t
         }
     if (mode > 7)
     {
-        for (int i = 0; i < 4; i++)
-            dst[i] = make_uint4(0, 0, 0, 0);
+        for (int px = 0; px < 16; px++)
+            pixels[px] = 0;
         return;
     }
     // mode table of the format (reference BC67.cpp:108-123)
@@ -148,7 +146,6 @@ __global__ void cvttmi_decode_bc7_kernel(const uint8_t *__restrict__ bc, uint8_t
         idx2[px] = separateAlpha ? (int)br.get(alphaIndexBits - (px == 0 ? 1 : 0)) : 0;
 
     const u32 map2 = T->partition2[partition & 63], map3 = T->partition3[partition & 63];
-    u32 pixels[16];
     for (int px = 0; px < 16; px++)
     {
         int rgbWeight = bc7Weight(indexBits, idx[px]);
@@ -188,6 +185,18 @@ __global__ void cvttmi_decode_bc7_kernel(const uint8_t *__restrict__ bc, uint8_t
         }
         pixels[px] = ((u32)pixel[0] & 0xffu) | (((u32)pixel[1] & 0xffu) << 8) | (((u32)pixel[2] & 0xffu) << 16) | (((u32)pixel[3] & 0xffu) << 24);
     }
+}
+
+__global__ void cvttmi_decode_bc7_kernel(const uint8_t *__restrict__ bc, uint8_t *__restrict__ out, u32 numBlocks,
+                                         const CvttDeviceTables *__restrict__ T)
+{
+    const u32 block = blockIdx.x * blockDim.x + threadIdx.x;
+    if (block >= numBlocks)
+        return;
+    const uint4 raw = *reinterpret_cast<const uint4 *>(bc + (size_t)block * 16u);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)block * 64u);
+    u32 pixels[16];
+    bc7Block(raw, T, pixels);
     for (int i = 0; i < 4; i++)
         dst[i] = make_uint4(pixels[4 * i], pixels[4 * i + 1], pixels[4 * i + 2], pixels[4 * i + 3]);
 }
@@ -199,16 +208,11 @@ __device__ __forceinline__ int signExtend(int v, int bits)
     return v;
 }
 
+// one BC6H block -> 16 texels of PixelBlockF16 as two words each: (R | G << 16, B | 0x3C00 << 16)
 template <bool SIGNED>
-__global__ void cvttmi_decode_bc6h_kernel(const uint8_t *__restrict__ bc, uint8_t *__restrict__ out, u32 numBlocks,
-                                          const CvttDeviceTables *__restrict__ T)
+__device__ __forceinline__ void bc6hBlock(const uint4 raw, const CvttDeviceTables *__restrict__ T, uint2 dst[16])
 {
-    const u32 block = blockIdx.x * blockDim.x + threadIdx.x;
-    if (block >= numBlocks)
-        return;
-    const uint4 raw = *reinterpret_cast<const uint4 *>(bc + (size_t)block * 16u);
     BitReader br = {((u64)raw.y << 32) | raw.x, ((u64)raw.w << 32) | raw.z, 0};
-    uint2 *dst = reinterpret_cast<uint2 *>(out + (size_t)block * 128u);
 
     int modeBits = (int)(raw.x & 3u);
     if (modeBits != 0 && modeBits != 1)
@@ -355,6 +359,704 @@ __global__ void cvttmi_decode_bc6h_kernel(const uint8_t *__restrict__ bc, uint8_
         dst[px] = make_uint2(c[0] | (c[1] << 16), c[2] | 0x3c000000u);
     }
 }
+
+template <bool SIGNED>
+__global__ void cvttmi_decode_bc6h_kernel(const uint8_t *__restrict__ bc, uint8_t *__restrict__ out, u32 numBlocks,
+                                          const CvttDeviceTables *__restrict__ T)
+{
+    const u32 block = blockIdx.x * blockDim.x + threadIdx.x;
+    if (block >= numBlocks)
+        return;
+    const uint4 raw = *reinterpret_cast<const uint4 *>(bc + (size_t)block * 16u);
+    uint2 texels[16];
+    bc6hBlock<SIGNED>(raw, T, texels);
+    uint2 *dst = reinterpret_cast<uint2 *>(out + (size_t)block * 128u);
+    for (int px = 0; px < 16; px++)
+        dst[px] = texels[px];
+}
+
+// ---- every format (include/cvtt_mi355x.h, CVTTMI_FMT_*): texel decoders, the decode kernel, and the measure kernel that
+// decodes in registers and adds up the squared error against the source without writing texels to HBM.  Rules and the
+// reference lines they follow: INTEGRATION.md, "Decoding and measuring every format"; numpy restatement:
+// tests/texture_decode_ref.py. ----
+enum
+{
+    kBC7 = 0, kBC1 = 1, kBC6HU = 2, kBC6HS = 3, kETC2 = 4, kETC2RGBA = 5, kBC2 = 6, kBC3 = 7, kBC4U = 8, kBC4S = 9, kBC5U = 10,
+    kBC5S = 11, kETC1 = 12, kETC2PT = 13, kEAC = 14, kR11U = 15, kR11S = 16
+};
+template <int F> struct Fmt
+{
+    static constexpr bool hdr = F == kBC6HU || F == kBC6HS;
+    static constexpr bool r11 = F == kR11U || F == kR11S;
+    static constexpr bool snorm = F == kBC4S || F == kBC5S;
+    static constexpr u32 bcBytes = kCvttTextureFormats[F].bcBytes;
+    static constexpr u32 mask = kCvttTextureFormats[F].mask;
+};
+static_assert(kCvttTextureFormatCount == kR11S + 1 && kCvttTextureFormats[kR11U].texBytes == 32 && kCvttTextureFormats[kBC6HU].texBytes == 128,
+              "texture_formats.h and the format ids");
+
+// ReconstructLDRPrecise (reference IndexSelector.h:102-112): weights by the reference's linear index
+__device__ __forceinline__ int lerp256(int e0, int e1, int w) { return ((256 - w) * e0 + w * e1 + 128) >> 8; }
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ int bitsOf(u64 w, int shift, int n) { return (int)((w >> shift) & ((1ull << n) - 1ull)); }
+
+// BC1-BC3 colour: lo = c0 | c1 << 16, hi = the 2-bit indexes.  BC2 / BC3 colour is always four-colour.
+__device__ __forceinline__ void bc1Colour(u32 lo, u32 hi, bool fourOnly, int px[16][4])
+{
+    const int c0 = (int)(lo & 0xffffu), c1 = (int)(lo >> 16);
+    int e0[3], e1[3];
+    {
+        const int r0 = (c0 >> 11) & 31, g0 = (c0 >> 5) & 63, b0 = c0 & 31, r1 = (c1 >> 11) & 31, g1 = (c1 >> 5) & 63, b1 = c1 & 31;
+        e0[0] = (r0 << 3) | (r0 >> 2); e0[1] = (g0 << 2) | (g0 >> 4); e0[2] = (b0 << 3) | (b0 >> 2); // S3TC.cpp:52-62
+        e1[0] = (r1 << 3) | (r1 >> 2); e1[1] = (g1 << 2) | (g1 >> 4); e1[2] = (b1 << 3) | (b1 >> 2);
+    }
+    const bool four = fourOnly || c0 > c1;
+#pragma unroll
+    for (int p = 0; p < 16; p++)
+    {
+        const int i = (int)((hi >> (2 * p)) & 3u);
+        // file index -> weight: four colours 0 / 256 / 85 / 171, three colours 0 / 256 / 128 (+ index 3 transparent)
+        const int w = four ? (i == 0 ? 0 : i == 1 ? 256 : i == 2 ? 85 : 171) : (i == 0 ? 0 : i == 1 ? 256 : 128);
+        const bool transparent = !four && i == 3;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            px[p][c] = transparent ? 0 : lerp256(e0[c], e1[c], w);
+        px[p][3] = transparent ? 0 : 255;
+    }
+}
+
+// BC3 alpha / BC4 / BC5 channel (PackInterpolatedAlpha, S3TC.cpp:343-715): 64-bit little-endian block -> 0..255, or
+// -127..127 signed (endpoints read as int8, -128 as -127, ramps in the biased domain 0..254 of Util::BiasSignedInput)
+template <bool SIGNED>
+__device__ __forceinline__ void interpAlpha(u64 a, int out[16])
+{
+    int e0, e1;
+    bool full;
+    if (SIGNED)
+    {
+        const int r0 = (int)(signed char)(a & 0xffu), r1 = (int)(signed char)((a >> 8) & 0xffu);
+        full = r0 > r1;
+        e0 = (r0 < -127 ? -127 : r0) + 127;
+        e1 = (r1 < -127 ? -127 : r1) + 127;
+    }
+    else
+    {
+        e0 = (int)(a & 0xffu);
+        e1 = (int)((a >> 8) & 0xffu);
+        full = e0 > e1;
+    }
+    const int high = SIGNED ? 254 : 255;
+#pragma unroll
+    for (int p = 0; p < 16; p++)
+    {
+        const int i = (int)((a >> (16 + 3 * p)) & 7u);
+        int v;
+        if (full)
+        {
+            const int k = i == 0 ? 0 : i == 1 ? 7 : i - 1; // weights (4681 k + 64) >> 7
+            const int w = k == 0 ? 0 : k == 1 ? 37 : k == 2 ? 73 : k == 3 ? 110 : k == 4 ? 146 : k == 5 ? 183 : k == 6 ? 219 : 256;
+            v = lerp256(e0, e1, w);
+        }
+        else
+        {
+            const int k = i == 0 ? 0 : i == 1 ? 5 : i - 1; // weights (6554 k + 64) >> 7
+            const int w = k == 0 ? 0 : k == 1 ? 51 : k == 2 ? 102 : k == 3 ? 154 : k == 4 ? 205 : 256;
+            v = i == 6 ? 0 : i == 7 ? high : lerp256(e0, e1, w);
+        }
+        out[p] = SIGNED ? v - 127 : v;
+    }
+}
+
+// ETC1 / ETC2 RGB / ETC2 punch-through colour block, w = the block's 8 bytes as a big-endian word.  Texel p = 4 y + x
+// takes its index from bit 4 x + y (and 16 + 4 x + y).  ETC1 decodes with the ETC2 rules (its encoder never overflows).
+template <bool PT>
+__device__ __forceinline__ void etcColour(u64 w, const CvttDeviceTables *__restrict__ T, int px[16][4])
+{
+    const bool diffBit = ((w >> 33) & 1u) != 0, flip = ((w >> 32) & 1u) != 0;
+    const bool differential = PT || diffBit, opaque = !PT || diffBit;
+    const int rb = bitsOf(w, 59, 5), gb = bitsOf(w, 51, 5), bb = bitsOf(w, 43, 5);
+    const int dr = bitsOf(w, 56, 3), dg = bitsOf(w, 48, 3), db = bitsOf(w, 40, 3);
+    const int r2 = rb + (dr >= 4 ? dr - 8 : dr), g2 = gb + (dg >= 4 ? dg - 8 : dg), b2 = bb + (db >= 4 ? db - 8 : db);
+    const int mode = !differential ? 0 : (r2 < 0 || r2 > 31) ? 1 : (g2 < 0 || g2 > 31) ? 2 : (b2 < 0 || b2 > 31) ? 3 : 0;
+    if (mode == 3)
+    {
+        // planar: O, H, V in 6/7/6 bits, (x (H - O) + y (V - O) + 4 O + 2) >> 2
+        const int ro = bitsOf(w, 57, 6), go = (bitsOf(w, 56, 1) << 6) | bitsOf(w, 49, 6);
+        const int bo = (bitsOf(w, 48, 1) << 5) | (bitsOf(w, 43, 2) << 3) | bitsOf(w, 39, 3);
+        const int rh = (bitsOf(w, 34, 5) << 1) | bitsOf(w, 32, 1), gh = bitsOf(w, 25, 7), bh = bitsOf(w, 19, 6);
+        const int rv = bitsOf(w, 13, 6), gv = bitsOf(w, 6, 7), bv = bitsOf(w, 0, 6);
+        const int O[3] = {(ro << 2) | (ro >> 4), (go << 1) | (go >> 6), (bo << 2) | (bo >> 4)};
+        const int H[3] = {(rh << 2) | (rh >> 4), (gh << 1) | (gh >> 6), (bh << 2) | (bh >> 4)};
+        const int V[3] = {(rv << 2) | (rv >> 4), (gv << 1) | (gv >> 6), (bv << 2) | (bv >> 4)};
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+        {
+            const int x = p & 3, y = p >> 2;
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                px[p][c] = clamp255((x * (H[c] - O[c]) + y * (V[c] - O[c]) + 4 * O[c] + 2) >> 2);
+            px[p][3] = 255;
+        }
+        return;
+    }
+    int paint[4][3];
+    int base[2][3];
+    int tab[2];
+    if (mode == 1)
+    {
+        const int c1[3] = {((bitsOf(w, 59, 2) << 2) | bitsOf(w, 56, 2)) * 17, bitsOf(w, 52, 4) * 17, bitsOf(w, 48, 4) * 17};
+        const int c2[3] = {bitsOf(w, 44, 4) * 17, bitsOf(w, 40, 4) * 17, bitsOf(w, 36, 4) * 17};
+        const int d = T->thDistance[(bitsOf(w, 34, 2) << 1) | bitsOf(w, 32, 1)];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            paint[0][c] = c1[c];
+            paint[1][c] = clamp255(c2[c] + d);
+            paint[2][c] = c2[c];
+            paint[3][c] = clamp255(c2[c] - d);
+        }
+    }
+    else if (mode == 2)
+    {
+        const int h1[3] = {bitsOf(w, 59, 4), (bitsOf(w, 56, 3) << 1) | bitsOf(w, 52, 1), (bitsOf(w, 51, 1) << 3) | bitsOf(w, 47, 3)};
+        const int h2[3] = {bitsOf(w, 43, 4), bitsOf(w, 39, 4), bitsOf(w, 35, 4)};
+        const int v1 = (h1[0] << 8) | (h1[1] << 4) | h1[2], v2 = (h2[0] << 8) | (h2[1] << 4) | h2[2];
+        const int d = T->thDistance[(bitsOf(w, 34, 1) << 2) | (bitsOf(w, 32, 1) << 1) | (v1 >= v2 ? 1 : 0)];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            paint[0][c] = clamp255(h1[c] * 17 + d);
+            paint[1][c] = clamp255(h1[c] * 17 - d);
+            paint[2][c] = clamp255(h2[c] * 17 + d);
+            paint[3][c] = clamp255(h2[c] * 17 - d);
+        }
+    }
+    else
+    {
+        const int sh1[3] = {60, 52, 44}, sh2[3] = {56, 48, 40};
+        const int b5[3] = {rb, gb, bb}, s5[3] = {r2, g2, b2};
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            if (differential)
+            {
+                base[0][c] = (b5[c] << 3) | (b5[c] >> 2);
+                base[1][c] = (s5[c] << 3) | (s5[c] >> 2);
+            }
+            else
+            {
+                base[0][c] = bitsOf(w, sh1[c], 4) * 17;
+                base[1][c] = bitsOf(w, sh2[c], 4) * 17;
+            }
+        }
+        tab[0] = bitsOf(w, 37, 3);
+        tab[1] = bitsOf(w, 34, 3);
+    }
+#pragma unroll
+    for (int p = 0; p < 16; p++)
+    {
+        const int x = p & 3, y = p >> 2, slot = 4 * x + y;
+        const int idx = (bitsOf(w, 16 + slot, 1) << 1) | bitsOf(w, slot, 1);
+        int rgb[3];
+        if (mode == 0)
+        {
+            const int sub = (flip ? y : x) >= 2 ? 1 : 0;
+            const int t = sub ? tab[1] : tab[0];
+            // etc1Modifiers[t] = {-large, -small, +small, +large}; index 0 +small, 1 +large, 2 -small, 3 -large
+            int mod = T->etc1Modifiers[t][idx == 0 ? 2 : idx == 1 ? 3 : idx == 2 ? 1 : 0];
+            mod = (!opaque && idx == 0) ? 0 : mod;
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                rgb[c] = clamp255((sub ? base[1][c] : base[0][c]) + mod);
+        }
+        else
+        {
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                rgb[c] = idx == 0 ? paint[0][c] : idx == 1 ? paint[1][c] : idx == 2 ? paint[2][c] : paint[3][c];
+        }
+        const bool transparent = !opaque && idx == 2;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            px[p][c] = transparent ? 0 : rgb[c];
+        px[p][3] = transparent ? 0 : 255;
+    }
+}
+
+// EAC (big-endian word): KIND 0 = 8-bit alpha 0..255, 1 = R11 unsigned 0..2047, 2 = R11 signed -1023..1023
+// (QuantizeETC2Alpha, reference ETC.cpp:2366-2404: base + modifier x multiplier; 11 bits: base 8 b + 4 / 8 b, multiplier 8 m,
+// or 1 when m = 0)
+template <int KIND>
+__device__ __forceinline__ void eacBlock(u64 w, const CvttDeviceTables *__restrict__ T, int out[16])
+{
+    const int base = bitsOf(w, 56, 8), mult = bitsOf(w, 52, 4), table = bitsOf(w, 48, 4);
+    const u32 pos = T->eacPosWord[table];
+#pragma unroll
+    for (int p = 0; p < 16; p++)
+    {
+        const int slot = 4 * (p & 3) + (p >> 2);
+        const int i = bitsOf(w, 45 - 3 * slot, 3);
+        const int pv = (int)((pos >> (8 * (i & 3))) & 0xffu);
+        const int mod = i >= 4 ? pv : -pv - 1;
+        int v;
+        if (KIND == 0)
+            v = clamp255(base + mod * mult);
+        else if (KIND == 1)
+        {
+            v = base * 8 + 4 + (mult == 0 ? mod : mod * mult * 8);
+            v = v < 0 ? 0 : (v > 2047 ? 2047 : v);
+        }
+        else
+        {
+            int sb = base >= 128 ? base - 256 : base;
+            sb = sb < -127 ? -127 : sb;
+            v = sb * 8 + (mult == 0 ? mod : mod * mult * 8);
+            v = v < -1023 ? -1023 : (v > 1023 ? 1023 : v);
+        }
+        out[p] = v;
+    }
+}
+
+__device__ __forceinline__ u64 bigEndian64(u32 lo, u32 hi) { return ((u64)__builtin_bswap32(lo) << 32) | (u64)__builtin_bswap32(hi); }
+
+// One packed block (raw: its 8 or 16 bytes as little-endian words) -> px[16][4]: 8-bit formats as 0..255 (BC4S / BC5S
+// -127..127), R11 in px[p][0], BC6H the half bit patterns.
+template <int F>
+__device__ __forceinline__ void decodeTexels(const uint4 raw, const CvttDeviceTables *__restrict__ T, int px[16][4])
+{
+    if (F == kBC7)
+    {
+        u32 pixels[16];
+        bc7Block(raw, T, pixels);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                px[p][c] = (int)((pixels[p] >> (8 * c)) & 0xffu);
+    }
+    else if (F == kBC6HU || F == kBC6HS)
+    {
+        uint2 t[16];
+        bc6hBlock<F == kBC6HS>(raw, T, t);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+        {
+            px[p][0] = (int)(t[p].x & 0xffffu);
+            px[p][1] = (int)(t[p].x >> 16);
+            px[p][2] = (int)(t[p].y & 0xffffu);
+            px[p][3] = 0x3c00;
+        }
+    }
+    else if (F == kBC1)
+        bc1Colour(raw.x, raw.y, false, px);
+    else if (F == kBC2 || F == kBC3)
+    {
+        bc1Colour(raw.z, raw.w, true, px);
+        if (F == kBC2)
+        {
+#pragma unroll
+            for (int p = 0; p < 16; p++)
+                px[p][3] = (int)(((p < 8 ? raw.x : raw.y) >> (4 * (p & 7))) & 15u) * 17;
+        }
+        else
+        {
+            int a[16];
+            interpAlpha<false>(((u64)raw.y << 32) | raw.x, a);
+#pragma unroll
+            for (int p = 0; p < 16; p++)
+                px[p][3] = a[p];
+        }
+    }
+    else if (F == kBC4U || F == kBC4S || F == kBC5U || F == kBC5S)
+    {
+        constexpr bool sg = F == kBC4S || F == kBC5S;
+        int r[16], g[16];
+        interpAlpha<sg>(((u64)raw.y << 32) | raw.x, r);
+        if (F == kBC5U || F == kBC5S)
+            interpAlpha<sg>(((u64)raw.w << 32) | raw.z, g);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+        {
+            px[p][0] = r[p];
+            px[p][1] = (F == kBC5U || F == kBC5S) ? g[p] : 0;
+            px[p][2] = 0;
+            px[p][3] = sg ? 127 : 255;
+        }
+    }
+    else if (F == kETC1 || F == kETC2)
+        etcColour<false>(bigEndian64(raw.x, raw.y), T, px);
+    else if (F == kETC2PT)
+        etcColour<true>(bigEndian64(raw.x, raw.y), T, px);
+    else if (F == kETC2RGBA)
+    {
+        etcColour<false>(bigEndian64(raw.z, raw.w), T, px);
+        int a[16];
+        eacBlock<0>(bigEndian64(raw.x, raw.y), T, a);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+            px[p][3] = a[p];
+    }
+    else if (F == kEAC)
+    {
+        int a[16];
+        eacBlock<0>(bigEndian64(raw.x, raw.y), T, a);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+        {
+            px[p][0] = px[p][1] = px[p][2] = 0;
+            px[p][3] = a[p];
+        }
+    }
+    else
+    {
+        int v[16];
+        eacBlock<F == kR11U ? 1 : 2>(bigEndian64(raw.x, raw.y), T, v);
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+        {
+            px[p][0] = v[p];
+            px[p][1] = px[p][2] = px[p][3] = 0;
+        }
+    }
+}
+
+template <int F>
+__device__ __forceinline__ uint4 loadPacked(const uint8_t *__restrict__ bc, size_t block)
+{
+    if (Fmt<F>::bcBytes == 8u)
+    {
+        const uint2 v = *reinterpret_cast<const uint2 *>(bc + block * 8u);
+        return make_uint4(v.x, v.y, 0u, 0u);
+    }
+    return *reinterpret_cast<const uint4 *>(bc + block * 16u);
+}
+
+// (BC7 and BC6H decode through the kernels above)
+template <int F>
+__global__ __launch_bounds__(256) void cvttmi_decode_kernel(const uint8_t *__restrict__ bc, uint8_t *__restrict__ out, u32 numBlocks,
+                                                          const CvttDeviceTables *__restrict__ T)
+{
+    static_assert(!Fmt<F>::hdr && F != kBC7, "BC7 / BC6H: cvttmi_launch_decode");
+    const u32 block = blockIdx.x * blockDim.x + threadIdx.x;
+    if (block >= numBlocks)
+        return;
+    int px[16][4];
+    decodeTexels<F>(loadPacked<F>(bc, block), T, px);
+    if (Fmt<F>::r11)
+    {
+        uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)block * 32u);
+        u32 h[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            h[i] = ((u32)px[2 * i][0] & 0xffffu) | (((u32)px[2 * i + 1][0] & 0xffffu) << 16);
+        dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
+        dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    }
+    else
+    {
+        uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)block * 64u);
+        u32 q[16];
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+            q[p] = ((u32)px[p][0] & 0xffu) | (((u32)px[p][1] & 0xffu) << 8) | (((u32)px[p][2] & 0xffu) << 16) | (((u32)px[p][3] & 0xffu) << 24);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            dst[i] = make_uint4(q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]);
+    }
+}
+
+// half bits -> float (exact)
+__device__ __forceinline__ float halfToFloat(int bits) { return __half2float(__ushort_as_half((unsigned short)(bits & 0xffff))); }
+
+// The source texels of one block as the encoder reads them.  SRC 0: the encoder's input blocks; 1: a linear RGBA8 image;
+// 2: a linear RGBA16F image (texels outside width x height are flagged invalid and count nowhere).
+struct MeasureImage
+{
+    const uint8_t *image;
+    size_t pitch;
+    u32 width, height, blocksPerRow;
+    size_t firstBlock; // image block of the launch's block 0
+};
+
+template <int F>
+__device__ __forceinline__ int sourceValue(u32 word, int c)
+{
+    // 8-bit sources: BC4S / BC5S read int8 with -128 as -127 (Util::BiasSignedInput)
+    const int b = (int)((word >> (8 * c)) & 0xffu);
+    if (Fmt<F>::snorm)
+    {
+        const int s = b >= 128 ? b - 256 : b;
+        return s < -127 ? -127 : s;
+    }
+    return b;
+}
+
+constexpr u32 kMeasureWG = 256;
+constexpr u32 kTotalWG = 1024; // lanes of the one-workgroup total
+constexpr u32 kMeasureLaunch = 1u << 24; // blocks per launch: the slab holds kMeasureLaunch / kMeasureWG partials
+
+template <int F, int SRC>
+__global__ __launch_bounds__(256) void cvttmi_measure_kernel(const uint8_t *__restrict__ bc, const uint8_t *__restrict__ source,
+                                                           const MeasureImage img, u32 numBlocks, void *__restrict__ blockError,
+                                                           void *__restrict__ slab, const CvttDeviceTables *__restrict__ T)
+{
+    typedef typename std::conditional<Fmt<F>::hdr, double, u64>::type Acc;
+    __shared__ Acc part[4][kMeasureWG];
+    const u32 tid = threadIdx.x;
+    const u32 block = blockIdx.x * kMeasureWG + tid;
+    Acc ch[4] = {0, 0, 0, 0};
+    if (block < numBlocks)
+    {
+        int px[16][4];
+        decodeTexels<F>(loadPacked<F>(bc, block), T, px);
+        u32 valid = 0xffffu;
+        if (Fmt<F>::hdr)
+        {
+            // float per block: texel 0..15, channel 0..2 inside; per channel: texel 0..15
+            float src[16][3];
+            if (SRC == 0)
+            {
+                const uint2 *s = reinterpret_cast<const uint2 *>(source + (size_t)block * 128u);
+#pragma unroll
+                for (int p = 0; p < 16; p++)
+                {
+                    const uint2 v = s[p];
+                    src[p][0] = halfToFloat((int)(v.x & 0xffffu));
+                    src[p][1] = halfToFloat((int)(v.x >> 16));
+                    src[p][2] = halfToFloat((int)(v.y & 0xffffu));
+                }
+            }
+            else
+            {
+                const size_t ib = img.firstBlock + block;
+                const u32 bx = (u32)(ib % img.blocksPerRow), by = (u32)(ib / img.blocksPerRow);
+                valid = 0;
+#pragma unroll
+                for (int p = 0; p < 16; p++)
+                {
+                    const u32 x = bx * 4u + (u32)(p & 3), y = by * 4u + (u32)(p >> 2);
+                    uint2 v = make_uint2(0u, 0u);
+                    if (x < img.width && y < img.height)
+                    {
+                        v = *reinterpret_cast<const uint2 *>(img.image + (size_t)y * img.pitch + (size_t)x * 8u);
+                        valid |= 1u << p;
+                    }
+                    src[p][0] = halfToFloat((int)(v.x & 0xffffu));
+                    src[p][1] = halfToFloat((int)(v.x >> 16));
+                    src[p][2] = halfToFloat((int)(v.y & 0xffffu));
+                }
+            }
+            float total = 0.0f, per[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int p = 0; p < 16; p++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                {
+                    const float d = halfToFloat(px[p][c]) - src[p][c];
+                    const float sq = ((valid >> p) & 1u) ? d * d : 0.0f;
+                    total = total + sq;
+                    per[c] = per[c] + sq;
+                }
+            if (blockError)
+                static_cast<float *>(blockError)[block] = total;
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                ch[c] = (Acc)per[c];
+        }
+        else
+        {
+            int src[16][4];
+            if (SRC == 0 && Fmt<F>::r11)
+            {
+                const uint4 *s = reinterpret_cast<const uint4 *>(source + (size_t)block * 32u);
+                const uint4 a = s[0], b = s[1];
+                const u32 wds[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int p = 0; p < 16; p++)
+                {
+                    int v = (int)(short)((wds[p >> 1] >> (16 * (p & 1))) & 0xffffu);
+                    // the encoder's clamp (reference ETC.cpp:2087-2113)
+                    if (F == kR11U)
+                        v = v < 0 ? 0 : (v > 2047 ? 2047 : v);
+                    else
+                        v = v < -1023 ? -1023 : (v > 1023 ? 1023 : v);
+                    src[p][0] = v;
+                    src[p][1] = src[p][2] = src[p][3] = 0;
+                }
+            }
+            else if (SRC == 0)
+            {
+                const uint4 *s = reinterpret_cast<const uint4 *>(source + (size_t)block * 64u);
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                {
+                    const uint4 v = s[i];
+                    const u32 wds[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+#pragma unroll
+                        for (int c = 0; c < 4; c++)
+                            src[4 * i + j][c] = sourceValue<F>(wds[j], c);
+                }
+            }
+            else
+            {
+                const size_t ib = img.firstBlock + block;
+                const u32 bx = (u32)(ib % img.blocksPerRow), by = (u32)(ib / img.blocksPerRow);
+                valid = 0;
+#pragma unroll
+                for (int p = 0; p < 16; p++)
+                {
+                    const u32 x = bx * 4u + (u32)(p & 3), y = by * 4u + (u32)(p >> 2);
+                    u32 v = 0;
+                    if (x < img.width && y < img.height)
+                    {
+                        v = *reinterpret_cast<const u32 *>(img.image + (size_t)y * img.pitch + (size_t)x * 4u);
+                        valid |= 1u << p;
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; c++)
+                        src[p][c] = sourceValue<F>(v, c);
+                }
+            }
+            u32 per[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int p = 0; p < 16; p++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    if ((Fmt<F>::mask >> c) & 1u)
+                    {
+                        const int d = px[p][c] - src[p][c];
+                        per[c] += ((valid >> p) & 1u) ? (u32)(d * d) : 0u;
+                    }
+            if (blockError)
+                static_cast<u32 *>(blockError)[block] = per[0] + per[1] + per[2] + per[3];
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                ch[c] = (Acc)per[c];
+        }
+    }
+    // one partial per workgroup: halving tree in LDS (the order cvtt_mi355x.h documents)
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        part[c][tid] = ch[c];
+    __syncthreads();
+    for (u32 s = kMeasureWG / 2; s > 0; s >>= 1)
+    {
+        if (tid < s)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                part[c][tid] = part[c][tid] + part[c][tid + s];
+        __syncthreads();
+    }
+    if (tid < 4)
+        static_cast<Acc *>(slab)[(size_t)blockIdx.x * 4u + tid] = part[tid][0];
+}
+
+// One workgroup of 1024 lanes: lane t adds the partials t, t + 1024, t + 2048, ... of a launch in that order (the loads of
+// eight of them are issued before their adds: with one dependent load per trip, 65 536 partials took 100 us), then a halving
+// tree in LDS as above, then into the totals (accumulate: added to what the previous launch of the call wrote).
+template <bool HDR>
+__global__ __launch_bounds__(1024) void cvttmi_measure_total_kernel(const void *__restrict__ slab, u32 numPartials, cvttmi_error_totals *totals,
+                                                                  int accumulate, u64 texels, u32 mask, int format)
+{
+    typedef typename std::conditional<HDR, double, u64>::type Acc;
+    __shared__ Acc part[4][kTotalWG];
+    const u32 tid = threadIdx.x;
+    const Acc *p = static_cast<const Acc *>(slab);
+    Acc acc[4] = {0, 0, 0, 0};
+    constexpr u32 kRows = 8;
+    for (u32 base = tid; base < numPartials; base += kRows * kTotalWG)
+    {
+        Acc v[kRows][4];
+#pragma unroll
+        for (u32 r = 0; r < kRows; r++)
+        {
+            const u32 i = base + r * kTotalWG;
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                v[r][c] = i < numPartials ? p[(size_t)i * 4u + c] : (Acc)0; // (adding 0 leaves a sum of non-negative terms as it is)
+        }
+#pragma unroll
+        for (u32 r = 0; r < kRows; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                acc[c] = acc[c] + v[r][c];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        part[c][tid] = acc[c];
+    __syncthreads();
+    for (u32 s = kTotalWG / 2; s > 0; s >>= 1)
+    {
+        if (tid < s)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                part[c][tid] = part[c][tid] + part[c][tid + s];
+        __syncthreads();
+    }
+    if (tid == 0)
+    {
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            const Acc v = ((mask >> c) & 1u) ? part[c][0] : (Acc)0;
+            if (HDR)
+            {
+                totals->sse[c] = 0;
+                totals->sseHdr[c] = (accumulate ? totals->sseHdr[c] : 0.0) + (double)v;
+            }
+            else
+            {
+                totals->sse[c] = (accumulate ? totals->sse[c] : 0ull) + (u64)v;
+                totals->sseHdr[c] = 0.0;
+            }
+        }
+        totals->texels = (accumulate ? totals->texels : 0ull) + texels;
+        totals->channelMask = mask;
+        totals->format = format;
+    }
+}
+
+template <int F>
+hipError_t launchDecodeFormat(const void *d_bc, void *d_out, u32 numBlocks, const CvttDeviceTables *T, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cvttmi_decode_kernel<F>, dim3((numBlocks + 255u) / 256u), dim3(256), 0, stream, (const uint8_t *)d_bc, (uint8_t *)d_out,
+                       numBlocks, T);
+    return hipGetLastError();
+}
+
+template <int F, int SRC>
+hipError_t launchMeasureFormat(const void *d_bc, const void *d_source, const MeasureImage &img, u32 numBlocks, void *d_blockError,
+                               void *d_slab, cvttmi_error_totals *d_totals, int accumulate, u64 texels, const CvttDeviceTables *T,
+                               hipStream_t stream)
+{
+    const u32 groups = (numBlocks + kMeasureWG - 1u) / kMeasureWG;
+    if (groups)
+    {
+        hipLaunchKernelGGL((cvttmi_measure_kernel<F, SRC>), dim3(groups), dim3(kMeasureWG), 0, stream, (const uint8_t *)d_bc,
+                           (const uint8_t *)d_source, img, numBlocks, d_blockError, d_slab, T);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(cvttmi_measure_total_kernel<Fmt<F>::hdr>, dim3(1), dim3(kTotalWG), 0, stream, (const void *)d_slab, groups, d_totals,
+                       accumulate, texels, Fmt<F>::mask, F);
+    return hipGetLastError();
+}
+
+template <int F>
+hipError_t measureBySource(int src, const void *d_bc, const void *d_source, const MeasureImage &img, u32 numBlocks, void *d_blockError,
+                           void *d_slab, cvttmi_error_totals *d_totals, int accumulate, u64 texels, const CvttDeviceTables *T, hipStream_t stream)
+{
+    if (src == 0)
+        return launchMeasureFormat<F, 0>(d_bc, d_source, img, numBlocks, d_blockError, d_slab, d_totals, accumulate, texels, T, stream);
+    // image forms: RGBA16F for BC6H, RGBA8 for every 8-bit format, none for R11 (the shim rejects other pairs)
+    constexpr int imageSrc = Fmt<F>::hdr ? 2 : 1;
+    if (Fmt<F>::r11 || src != imageSrc)
+        return hipErrorInvalidValue;
+    return launchMeasureFormat<F, Fmt<F>::r11 ? 0 : imageSrc>(d_bc, d_source, img, numBlocks, d_blockError, d_slab, d_totals, accumulate, texels, T, stream);
+}
 } // namespace
 
 extern "C" hipError_t cvttmi_launch_decode(const void *d_bc, void *d_out, uint32_t numBlocks, int format,
@@ -370,4 +1072,67 @@ extern "C" hipError_t cvttmi_launch_decode(const void *d_bc, void *d_out, uint32
     else
         hipLaunchKernelGGL(cvttmi_decode_bc6h_kernel<true>, grid, block, 0, stream, (const uint8_t *)d_bc, (uint8_t *)d_out, numBlocks, d_tables);
     return hipGetLastError();
+}
+
+// every format: 0 .. CVTTMI_FMT_COUNT - 1.  BC7 and BC6H go through the kernels above, so their output stays that of
+// cvttmi_decode_bc7 / bc6h byte for byte.
+extern "C" hipError_t cvttmi_launch_decode_format(const void *d_bc, void *d_out, uint32_t numBlocks, int format,
+                                                  const CvttDeviceTables *d_tables, hipStream_t stream)
+{
+    switch (format)
+    {
+    case kBC7: return cvttmi_launch_decode(d_bc, d_out, numBlocks, 0, d_tables, stream);
+    case kBC6HU: return cvttmi_launch_decode(d_bc, d_out, numBlocks, 1, d_tables, stream);
+    case kBC6HS: return cvttmi_launch_decode(d_bc, d_out, numBlocks, 2, d_tables, stream);
+    }
+    if (numBlocks == 0)
+        return hipSuccess;
+    switch (format)
+    {
+    case kBC1: return launchDecodeFormat<kBC1>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kETC2: return launchDecodeFormat<kETC2>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kETC2RGBA: return launchDecodeFormat<kETC2RGBA>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC2: return launchDecodeFormat<kBC2>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC3: return launchDecodeFormat<kBC3>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC4U: return launchDecodeFormat<kBC4U>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC4S: return launchDecodeFormat<kBC4S>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC5U: return launchDecodeFormat<kBC5U>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kBC5S: return launchDecodeFormat<kBC5S>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kETC1: return launchDecodeFormat<kETC1>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kETC2PT: return launchDecodeFormat<kETC2PT>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kEAC: return launchDecodeFormat<kEAC>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kR11U: return launchDecodeFormat<kR11U>(d_bc, d_out, numBlocks, d_tables, stream);
+    case kR11S: return launchDecodeFormat<kR11S>(d_bc, d_out, numBlocks, d_tables, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// One launch of the measure (numBlocks <= 2^24, > 0) and its total: source 0 = blocks, 1 = RGBA8 image, 2 = RGBA16F image
+// (image: width, height, pitch, blocks per row = ceil(width / 4); d_bc starts at block firstBlock of the image).  d_slab: (2^24 / 256) x 4 x 8 bytes.
+extern "C" hipError_t cvttmi_launch_measure(const void *d_bc, const void *d_source, int source, uint32_t width, uint32_t height,
+                                            size_t pitch, size_t firstBlock, uint32_t numBlocks, int format, void *d_blockError, void *d_slab,
+                                            cvttmi_error_totals *d_totals, int accumulate, uint64_t texels,
+                                            const CvttDeviceTables *d_tables, hipStream_t stream)
+{
+    if (numBlocks > kMeasureLaunch)
+        return hipErrorInvalidValue;
+    MeasureImage img;
+    img.image = (const uint8_t *)d_source;
+    img.pitch = pitch;
+    img.width = width;
+    img.height = height;
+    img.blocksPerRow = (width + 3u) / 4u;
+    img.firstBlock = firstBlock;
+#define CVTTMI_MEASURE_CASE(F) \
+    case F: return measureBySource<F>(source, d_bc, d_source, img, numBlocks, d_blockError, d_slab, d_totals, accumulate, texels, d_tables, stream);
+    switch (format)
+    {
+        CVTTMI_MEASURE_CASE(kBC7) CVTTMI_MEASURE_CASE(kBC1) CVTTMI_MEASURE_CASE(kBC6HU) CVTTMI_MEASURE_CASE(kBC6HS)
+        CVTTMI_MEASURE_CASE(kETC2) CVTTMI_MEASURE_CASE(kETC2RGBA) CVTTMI_MEASURE_CASE(kBC2) CVTTMI_MEASURE_CASE(kBC3)
+        CVTTMI_MEASURE_CASE(kBC4U) CVTTMI_MEASURE_CASE(kBC4S) CVTTMI_MEASURE_CASE(kBC5U) CVTTMI_MEASURE_CASE(kBC5S)
+        CVTTMI_MEASURE_CASE(kETC1) CVTTMI_MEASURE_CASE(kETC2PT) CVTTMI_MEASURE_CASE(kEAC) CVTTMI_MEASURE_CASE(kR11U)
+        CVTTMI_MEASURE_CASE(kR11S)
+    }
+#undef CVTTMI_MEASURE_CASE
+    return hipErrorInvalidValue;
 }

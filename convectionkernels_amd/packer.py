@@ -1,12 +1,15 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] input output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-metrics] input output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
 file, `-quality 1..100` for a BC7 plan).  The image is uploaded once; tiling into groups of eight 4x4 blocks with
 edge clamping (etc2packer.cpp:215-248), encoding and the removal of padding blocks all run on the device, and the
-packed blocks are already in container order.  The input is anything PIL opens, or a .npy of shape (H, W, 4) uint8."""
+packed blocks are already in container order.  The input is anything PIL opens, or a .npy of shape (H, W, 4) uint8.
+-metrics: after the file is written, print the encoding error to stdout, measured on the device against the input image
+(Context.measure_image: one line per measured channel with its MSE and PSNR, then the PSNR over all of them; R11 has no
+image form and is measured over the written blocks against their tiles, the clamped texels of the edge blocks included)."""
 import sys
 
 import numpy as np
@@ -57,9 +60,40 @@ def encode_file(image, fmt, options=None, plan=None, ctx=None):
     return packed.cpu().numpy()
 
 
+def measure_file(image, fmt, packed, options=None, ctx=None):
+    """ErrorReport of the packed blocks encode_file returned for `image`"""
+    import torch
+    ctx = ctx or api.default_context()
+    fmt = container.canonical(fmt)
+    if fmt in ("r11u", "r11s"):
+        # the written blocks (ceil(W/4) of each group-padded row) against their tiles; the packed count need not be a
+        # multiple of 8, so the measure runs over whole groups and only the written blocks' values are added up
+        tiles, bw, bh, gw = r11_blocks(image, fmt == "r11s")
+        tiles = tiles.reshape(bh, gw, 16)[:, :bw].reshape(-1, 16)
+        n = len(tiles)
+        pad = (-n) % api.NumParallelBlocks
+        src = np.concatenate([tiles, np.repeat(tiles[-1:], pad, axis=0)])
+        bc = np.concatenate([np.asarray(packed, np.uint8).reshape(-1, 8), np.repeat(np.asarray(packed, np.uint8).reshape(-1, 8)[-1:], pad, axis=0)])
+        rep = ctx.measure_error(fmt, src, bc, per_block=True)
+        totals = api.ErrorTotals()
+        totals.format, totals.channelMask, totals.texels = rep.totals.format, rep.totals.channelMask, 16 * n
+        totals.sse[0] = int(rep.per_block[:n].astype(np.uint64).sum())
+        return api.ErrorReport(fmt, totals, rep.per_block[:n])
+    dev = torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device)
+    return ctx.measure_image(fmt, dev, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
+
+
+def print_metrics(report, out=None):
+    out = out or sys.stdout
+    for c, name in enumerate("RGBA"):
+        if (report.channel_mask >> c) & 1:
+            out.write("%s mse %.6f psnr %.4f dB\n" % (name, report.mse[c], report.psnr(name)))
+    out.write("psnr %.4f dB (%s, %d texels)\n" % (report.psnr(), report.channels.upper(), report.texels))
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    fmt, uniform, fake, quality, dds, paths = "etc2rgb", False, False, None, False, []
+    fmt, uniform, fake, quality, dds, metrics, paths = "etc2rgb", False, False, None, False, False, []
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -73,6 +107,8 @@ def main(argv=None):
             uniform = True
         elif a == "-dds":
             dds = True
+        elif a == "-metrics":
+            metrics = True
         elif a == "-fakebt709":
             fake = True
         elif a.startswith("-"):
@@ -102,6 +138,8 @@ def main(argv=None):
     packed = encode_file(image, fmt, options, plan)
     h, w = image.shape[:2]
     (container.write_dds if dds else container.write_ktx)(paths[1], fmt, w, h, packed)
+    if metrics:
+        print_metrics(measure_file(image, fmt, packed, options))
     return 0
 
 

@@ -299,6 +299,63 @@ int cvttmi_decode_bc7(cvttmi_context *ctx, uint8_t *blocks, const uint8_t *bc, s
 int cvttmi_decode_bc6h_device(cvttmi_context *ctx, void *d_blocksF16, const void *d_bc, size_t numBlocks, int isSigned, void *hipStream);
 int cvttmi_decode_bc6h(cvttmi_context *ctx, uint8_t *blocksF16, const uint8_t *bc, size_t numBlocks, int isSigned);
 
+/* ---- every format: decode, and the encoding error in one pass (not part of the reference's API) ----
+ * format = CVTTMI_FMT_* below.  A decoder writes the layout its encoder reads:
+ *   BC7, BC1, BC2, BC3, ETC1, ETC2 RGB / RGBA / punch-through, EAC alpha: PixelBlockU8 (64 B; BC1 three-colour index 3 and
+ *     punch-through transparent texels = (0,0,0,0); ETC RGB alpha = 255; EAC alpha = (0,0,0,a))
+ *   BC4U / BC5U: PixelBlockU8 (r,0,0,255) / (r,g,0,255);  BC4S / BC5S: PixelBlockS8 (r,0,0,127) / (r,g,0,127)
+ *   BC6HU / BC6HS: PixelBlockF16 (128 B, alpha 0x3C00);  R11U / R11S: PixelBlockScalarS16 (32 B, 0..2047 / -1023..1023)
+ * Reconstruction follows the models the encoders score their candidates with ("Decoding and measuring").
+ * The measure reads each packed block and its source once, decodes in registers and adds up the squared difference of the
+ * channels the format stores (channelMask: BC1-3, BC7, ETC2 RGBA / punch-through RGBA; ETC1 / ETC2 RGB, BC6H RGB; BC5 RG;
+ * BC4, R11 R; EAC A).  The source is read exactly as the encoder reads it (BC4S / BC5S: int8, -128 as -127; R11: clamped to
+ * the encoder's range; BC6H: half -> float).
+ * Integer formats: per block a uint32, totals uint64, exact.  BC6H: per block a float, summed in float in the order texel
+ * 0..15, channel 0..2 inside; sseHdr[c] = double sums of the per-block float sums of channel c (texel 0..15), reduced in a
+ * fixed order: 256 blocks per workgroup, halving tree a[i] += a[i + s] (s = 128 .. 1), one partial per workgroup, then one
+ * workgroup of 1024 lanes sums a launch's partials (lane t: t, t + 1024, ... in order, then the halving tree s = 512 .. 1);
+ * launches of at most 2^24 blocks
+ * (host entries: chunks of 2^17) add into the totals in order.  No float atomics: the same input gives bit-identical totals
+ * on every run and stream.  The partials live in one slab per context: like the BC7 hand-over list, a call on another
+ * stream than the previous one waits for it (one context per stream to overlap work). ---- */
+#define CVTTMI_FMT_BC2 6
+#define CVTTMI_FMT_BC3 7
+#define CVTTMI_FMT_BC4U 8
+#define CVTTMI_FMT_BC4S 9
+#define CVTTMI_FMT_BC5U 10
+#define CVTTMI_FMT_BC5S 11
+#define CVTTMI_FMT_ETC1 12
+#define CVTTMI_FMT_ETC2_PUNCHTHROUGH 13
+#define CVTTMI_FMT_EAC_ALPHA 14
+#define CVTTMI_FMT_R11U 15
+#define CVTTMI_FMT_R11S 16
+#define CVTTMI_FMT_COUNT 17
+typedef struct cvttmi_error_totals
+{
+    uint64_t sse[4];      /* integer formats: exact per-channel sums; 0 for channels the format does not store */
+    double sseHdr[4];     /* BC6H only, summation order as documented above */
+    uint64_t texels;      /* texels counted per measured channel */
+    uint32_t channelMask; /* bit c = channel c is measured for this format */
+    int32_t format;
+} cvttmi_error_totals;
+/* numBlocks (multiple of 8) packed blocks -> the decoded layout above */
+int cvttmi_decode_device(cvttmi_context *ctx, int format, void *d_out, const void *d_bc, size_t numBlocks, void *hipStream);
+int cvttmi_decode(cvttmi_context *ctx, int format, void *out, const uint8_t *bc, size_t numBlocks);
+/* d_source: numBlocks blocks of the encoder's input layout.  d_blockError: NULL, or numBlocks uint32 (float for BC6H).
+ * d_totals: device memory (the host form: host memory) the totals are written to. */
+int cvttmi_measure_error_device(cvttmi_context *ctx, int format, const void *d_bc, const void *d_source, size_t numBlocks,
+                                void *d_blockError, cvttmi_error_totals *d_totals, void *hipStream);
+int cvttmi_measure_error(cvttmi_context *ctx, int format, const uint8_t *bc, const void *source, size_t numBlocks,
+                         void *blockError, cvttmi_error_totals *totals);
+/* d_bc: the ceil(W/4) x ceil(H/4) blocks, row-major, that encode_image / cvttmi_compact_rows_device produce; d_image: the
+ * linear RGBA8 (every format but BC6H and R11) or RGBA16F (BC6H) image.  Texels outside width x height count nowhere. */
+int cvttmi_measure_image_error_device(cvttmi_context *ctx, int format, const void *d_bc, const void *d_image, uint32_t width,
+                                      uint32_t height, size_t rowPitchBytes, int pixels, void *d_blockError,
+                                      cvttmi_error_totals *d_totals, void *hipStream);
+/* PSNR in dB over the channels of channelMask (0 = the format's channels): 10 log10(peak^2 / MSE), peak 255 (BC4S / BC5S 254,
+ * R11U 2047, R11S 2046); +inf on zero error; NaN for BC6H, for channels the format does not store and for no texels. */
+double cvttmi_psnr(const cvttmi_error_totals *t, uint32_t channelMask);
+
 /* ---- one job on several devices (csrc/multi.cpp).  The north-star's "large images shard by block row across the GPUs of one
  * node", for callers of this C interface (the reference has no counterpart: its callers parallelise by threads over groups,
  * etc2packer.cpp:215-281).  Groups of 8 blocks are independent, so the search needs no exchange: the job is cut into
