@@ -1426,7 +1426,8 @@ static void bc7_encode_group(const uint8_t *blocks, uint8_t *out, const orc_opti
 /* ------------------------------------------------------------------------------------
  * threading over groups
  * ---------------------------------------------------------------------------------- */
-typedef void (*group_fn)(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp);
+/* `group` is the index of the group of 8 blocks: a job that also hands out per-block results indexes them with it */
+typedef void (*group_fn)(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group);
 
 typedef struct
 {
@@ -1445,7 +1446,7 @@ static void *job_main(void *arg)
     unsigned csr = _mm_getcsr();
     _mm_setcsr((csr & ~_MM_ROUND_MASK) | _MM_ROUND_NEAREST); /* RoundTowardNearestForScope */
     for (size_t g = j->groupBegin; g < j->groupEnd; g++)
-        j->fn(j->in + g * j->inStride, j->out + g * j->outStride, j->a, j->b, j->rcp);
+        j->fn(j->in + g * j->inStride, j->out + g * j->outStride, j->a, j->b, j->rcp, g);
     _mm_setcsr(csr);
     return NULL;
 }
@@ -1483,8 +1484,9 @@ static void run_groups(group_fn fn, const uint8_t *in, uint8_t *out, size_t numG
     free(tids);
 }
 
-static void bc7_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+static void bc7_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
+    (void)group;
     bc7_encode_group(in, out, (const orc_options *)a, (const orc_bc7_plan *)b, rcp);
 }
 
@@ -1507,3 +1509,27 @@ int orc_encode_bc7(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const 
 #include "cvtt_oracle_s3tc.inc"
 #include "cvtt_oracle_bc6h.inc"
 #include "cvtt_oracle_etc2.inc"
+
+/* ------------------------------------------------------------------------------------
+ * the same encodes, also handing out each block's final error: the score of the candidate whose bytes are written.
+ * The bytes are those of the plain entry points.  Every array is indexed by block, so any `threads` is fine; a NULL
+ * array is not written.  With ORC_FLAG_UNIFORM set and S3TC_Paranoid / S3TC_Exhaustive clear the score is a plain sum
+ * of squared integer differences (at most 16 * 3 * 255^2 < 2^24, exact in a float).
+ * ---------------------------------------------------------------------------------- */
+int orc_encode_bc1_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                       const float *rcp17, int threads, float *err)
+{
+    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, err);
+}
+
+int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
+                        const float *rcp17, int threads, float *colorErr, float *alphaErr)
+{
+    return s3tc_encode(out, blocks, numBlocks, options, format, rcp17, threads, colorErr, alphaErr);
+}
+
+int orc_encode_etc2_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                        const orc_options *allocOptions, int mode, int threads, float *colorErr, uint32_t *alphaErr)
+{
+    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, colorErr, alphaErr);
+}

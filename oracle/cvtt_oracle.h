@@ -92,6 +92,18 @@ int orc_encode_s3tc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const
 /* EAC R11 (cvtt::Kernels::EncodeETC2Alpha11): numBlocks * 16 int16 (PixelBlockScalarS16) -> 8 B/block */
 int orc_encode_eac11(uint8_t *out, const int16_t *blocksS16, size_t numBlocks, int isSigned);
 
+/* The same encodes (same bytes), also writing each block's final error -- the score of the candidate that is emitted --
+ * into caller-supplied arrays indexed by block (NULL = not wanted).
+ *   colorErr: one float per block: BC1, BC2 / BC3 colour, ETC1 and ETC2 colour (modes 0, 1, 3, 4)
+ *   alphaErr: s3tc: one float per block and interpolated channel (BC3, BC4: 1; BC5: 2; BC2 keeps none)
+ *             etc2: one uint32 per block, the EAC alpha error (modes 1, 2) */
+int orc_encode_bc1_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                       const float *rcp17, int threads, float *err);
+int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
+                        const float *rcp17, int threads, float *colorErr, float *alphaErr);
+int orc_encode_etc2_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                        const orc_options *allocOptions, int mode, int threads, float *colorErr, uint32_t *alphaErr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -475,8 +475,10 @@ static void s3tc_exhaustive_group(s3tc_lane_t *lanes, uint32_t flags, const floa
     }
 }
 
-/* PackRGB for a group of 8 blocks (outputs `stride` apart) */
-static void s3tc_pack_rgb_group(const uint8_t *blocks, uint8_t *out, size_t stride, const orc_options *options, const float *rcp, int alphaTest)
+/* PackRGB for a group of 8 blocks (outputs `stride` apart).  err: NULL, or 8 floats that receive each block's final
+ * bestError, the score of the candidate that is emitted. */
+static void s3tc_pack_rgb_group(const uint8_t *blocks, uint8_t *out, size_t stride, const orc_options *options, const float *rcp, int alphaTest,
+                                float *err)
 {
     static __thread s3tc_lane_t lanes[8];
     for (int l = 0; l < 8; l++)
@@ -488,6 +490,9 @@ static void s3tc_pack_rgb_group(const uint8_t *blocks, uint8_t *out, size_t stri
             s3tc_search(&lanes[l], options->flags, rcp, alphaTest);
     for (int l = 0; l < 8; l++)
         s3tc_emit(&lanes[l], out + l * stride);
+    if (err)
+        for (int l = 0; l < 8; l++)
+            err[l] = lanes[l].best.bestError;
 }
 
 static void s3tc_pack_rgb(const uint8_t *block, uint8_t *out, const orc_options *options, const float *rcp, int alphaTest)
@@ -498,14 +503,17 @@ static void s3tc_pack_rgb(const uint8_t *block, uint8_t *out, const orc_options 
     s3tc_emit(&ln, out);
 }
 
-static void bc1_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+typedef struct { const orc_options *options; float *err; /* NULL, or one float per block */ } bc1_job_t;
+
+static void bc1_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)b;
-    s3tc_pack_rgb_group(in, out, 8, (const orc_options *)a, rcp, 1);
+    const bc1_job_t *job = (const bc1_job_t *)a;
+    s3tc_pack_rgb_group(in, out, 8, job->options, rcp, 1, job->err ? job->err + group * 8 : NULL);
 }
 
-int orc_encode_bc1(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
-                   const float *rcp17, int threads)
+static int bc1_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                      const float *rcp17, int threads, float *err)
 {
     if (numBlocks % 8 != 0)
         return -1;
@@ -515,6 +523,13 @@ int orc_encode_bc1(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const 
         orc_probe_rcp(probed);
         rcp17 = probed;
     }
-    run_groups(bc1_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * 8, options, NULL, rcp17, threads);
+    bc1_job_t job = {options, err};
+    run_groups(bc1_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * 8, &job, NULL, rcp17, threads);
     return 0;
+}
+
+int orc_encode_bc1(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                   const float *rcp17, int threads)
+{
+    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, NULL);
 }

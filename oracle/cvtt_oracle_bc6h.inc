@@ -768,13 +768,15 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
         bc6h_emit(&lanes[l], out + l * 16);
 }
 
-static void bc6hu_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+static void bc6hu_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
+    (void)group;
     (void)b;
     bc6h_encode_group(in, out, (const orc_options *)a, 0, rcp);
 }
-static void bc6hs_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+static void bc6hs_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
+    (void)group;
     (void)b;
     bc6h_encode_group(in, out, (const orc_options *)a, 1, rcp);
 }

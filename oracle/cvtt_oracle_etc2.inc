@@ -1062,7 +1062,8 @@ static void etc1_cluster_fit(const etc_ctx_t *cx, etc_lane_t *ln, int minD)
 
 /* ---- EAC: 8-bit alpha and 11-bit R11 (CompressETC2AlphaBlockInternal, ETC.cpp:1902-2085; QuantizeETC2Alpha,
  * 2366-2411).  Integer only and lane independent; 16-bit lanes wrap like the reference's. ---- */
-static void eac_block(const int pixels[16], int is11Bit, int isSigned, uint8_t *out)
+/* errOut: NULL, or where the final bestTotalError (the score of the emitted table, base, multiplier and indexes) goes */
+static void eac_block(const int pixels[16], int is11Bit, int isSigned, uint8_t *out, uint32_t *errOut)
 {
     int minAlpha = is11Bit ? 2047 : 255, maxAlpha = 0;
     for (int px = 0; px < 16; px++)
@@ -1173,6 +1174,8 @@ static void eac_block(const int pixels[16], int is11Bit, int isSigned, uint8_t *
             }
         }
     }
+    if (errOut)
+        *errOut = bestTotalError;
     if (is11Bit)
     {
         bestMultiplier >>= 3;
@@ -1198,12 +1201,12 @@ static void eac_block(const int pixels[16], int is11Bit, int isSigned, uint8_t *
     }
 }
 
-static void etc2_alpha_block(const uint8_t *block, uint8_t *out)
+static void etc2_alpha_block(const uint8_t *block, uint8_t *out, uint32_t *errOut)
 {
     int pixels[16];
     for (int px = 0; px < 16; px++)
         pixels[px] = block[px * 4 + 3];
-    eac_block(pixels, 0, 0, out);
+    eac_block(pixels, 0, 0, out, errOut);
 }
 
 /* CompressEACBlock, ETC.cpp:2087-2114: PixelBlockScalarS16 -> shifted 11-bit range -> 8 bytes */
@@ -1229,7 +1232,7 @@ int orc_encode_eac11(uint8_t *out, const int16_t *blocksS16, size_t numBlocks, i
             }
             pixels[px] = v;
         }
-        eac_block(pixels, 1, isSigned, out + b * 8);
+        eac_block(pixels, 1, isSigned, out + b * 8, NULL);
     }
     return 0;
 }
@@ -1610,8 +1613,9 @@ static void etc1_punchthrough(const etc_ctx_t *cx, etc_lane_t *ln)
     put_be32(ln->out + 4, lowBits);
 }
 
-/* CompressETC2Block for one group, ETC.cpp:1664-1887 (cx->punchthrough selects EncodeETC2PunchthroughAlpha) */
-static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t outStride, const etc_ctx_t *cx)
+/* CompressETC2Block for one group, ETC.cpp:1664-1887 (cx->punchthrough selects EncodeETC2PunchthroughAlpha).
+ * err: NULL, or 8 floats that receive each block's final bestError, the score of the candidate that is emitted. */
+static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t outStride, const etc_ctx_t *cx, float *err)
 {
     static __thread etc_lane_t lanes[8];
     int groupAny = 0, groupAll = 1; /* AnySet(anyTransparent), AllSet(allTransparent) */
@@ -1722,11 +1726,14 @@ static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t 
     }
     for (int l = 0; l < 8; l++)
         memcpy(out + l * outStride, lanes[l].out, 8);
+    if (err)
+        for (int l = 0; l < 8; l++)
+            err[l] = lanes[l].bestError;
 }
 
 /* CompressETC1Block, ETC.cpp:2116-2126: lanes are independent (the group-wide padding of the candidate lists only
  * repeats a colour already tried, and repeats never pass the strict '<') */
-static void etc1_encode_group(const uint8_t *blocks, uint8_t *out, const etc_ctx_t *cx)
+static void etc1_encode_group(const uint8_t *blocks, uint8_t *out, const etc_ctx_t *cx, float *err)
 {
     static __thread etc_lane_t lane;
     for (int l = 0; l < 8; l++)
@@ -1746,6 +1753,8 @@ static void etc1_encode_group(const uint8_t *blocks, uint8_t *out, const etc_ctx
         memset(ln->out, 0, 8);
         etc1_cluster_fit(cx, ln, 0);
         memcpy(out + l * 8, ln->out, 8);
+        if (err)
+            err[l] = ln->bestError;
     }
 }
 
@@ -1753,27 +1762,31 @@ typedef struct
 {
     etc_ctx_t cx;
     int mode;
+    float *colorErr;    /* NULL, or one float per block (modes 0, 1, 3, 4) */
+    uint32_t *alphaErr; /* NULL, or one uint32 per block (modes 1, 2) */
 } etc_job_t;
 
-static void etc2_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+static void etc2_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)b;
     (void)rcp;
     const etc_job_t *job = (const etc_job_t *)a;
+    float *cerr = job->colorErr ? job->colorErr + group * 8 : NULL;
+    uint32_t *aerr = job->alphaErr ? job->alphaErr + group * 8 : NULL;
     if (job->mode == 0 || job->mode == 4)
-        etc2_encode_group_color(in, out, 8, &job->cx);
+        etc2_encode_group_color(in, out, 8, &job->cx, cerr);
     else if (job->mode == 3)
-        etc1_encode_group(in, out, &job->cx);
+        etc1_encode_group(in, out, &job->cx, cerr);
     else if (job->mode == 1)
     {
         /* EncodeETC2RGBA, API.cpp:270-286: [alpha 8 B | colour 8 B] */
-        etc2_encode_group_color(in, out + 8, 16, &job->cx);
+        etc2_encode_group_color(in, out + 8, 16, &job->cx, cerr);
         for (int l = 0; l < 8; l++)
-            etc2_alpha_block(in + l * 64, out + l * 16);
+            etc2_alpha_block(in + l * 64, out + l * 16, aerr ? aerr + l : NULL);
     }
     else
         for (int l = 0; l < 8; l++)
-            etc2_alpha_block(in + l * 64, out + l * 8);
+            etc2_alpha_block(in + l * 64, out + l * 8, aerr ? aerr + l : NULL);
 }
 
 int orc_encode_etc2(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int mode, int threads)
@@ -1783,13 +1796,15 @@ int orc_encode_etc2(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const
 
 /* allocOptions: the Options AllocETC2Data was called with; the two chroma axes are computed from ITS colour weights when the
  * scratch is constructed (ETC.cpp:3117-3145), everything else comes from the Options of the Encode call */
-int orc_encode_etc2_alloc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
-                          int mode, int threads)
+static int etc2_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
+                       int mode, int threads, float *colorErr, uint32_t *alphaErr)
 {
     if (numBlocks % 8 != 0 || mode < 0 || mode > 4) /* 3 = ETC1 (EncodeETC1, API.cpp:201-214), 4 = EncodeETC2PunchthroughAlpha (231-244) */
         return -1;
     etc_job_t job;
     job.mode = mode;
+    job.colorErr = mode == 2 ? NULL : colorErr;
+    job.alphaErr = (mode == 1 || mode == 2) ? alphaErr : NULL;
     job.cx.flags = options->flags;
     job.cx.uniform = (options->flags & ORC_FLAG_UNIFORM) != 0;
     job.cx.fake = (options->flags & 0x400u) != 0;
@@ -1808,4 +1823,10 @@ int orc_encode_etc2_alloc(uint8_t *out, const uint8_t *blocks, size_t numBlocks,
     const size_t outPer = mode == 1 ? 16 : 8;
     run_groups(etc2_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * outPer, &job, NULL, NULL, threads);
     return 0;
+}
+
+int orc_encode_etc2_alloc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
+                          int mode, int threads)
+{
+    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, NULL, NULL);
 }

@@ -7,8 +7,9 @@
 /* ParallelMath::LessOrEqual(UInt15) is implemented as '<' (ParallelMath.h:740-745); only this path uses it */
 static inline int s3tc_le_u15(int a, int b) { return a < b; }
 
+/* errOut: NULL, or where the final bestError (the score of the emitted end points and indexes) goes */
 static void s3tc_interpolated_alpha(const uint8_t *block, int inputChannel, uint8_t *out, uint32_t flags, int isSigned,
-                                    int maxTweakRounds, int numRefineRounds, const float *rcp)
+                                    int maxTweakRounds, int numRefineRounds, const float *rcp, float *errOut)
 {
     (void)flags;
     if (maxTweakRounds < 1) maxTweakRounds = 1;
@@ -193,6 +194,8 @@ static void s3tc_interpolated_alpha(const uint8_t *block, int inputChannel, uint
             }
     }
 
+    if (errOut)
+        *errOut = bestError;
     int ep0 = bestEP[0], ep1 = bestEP[1];
     if (isSigned)
     {
@@ -245,17 +248,25 @@ static void s3tc_explicit_alpha(const uint8_t *block, int inputChannel, uint8_t 
 
 /* format: 2 = BC2, 3 = BC3, 4 = BC4U, 5 = BC4S, 6 = BC5U, 7 = BC5S.  Signed formats take PixelBlockS8 (biased like
  * Util::BiasSignedInput, Util.cpp:47-60).  Output 8 bytes (BC4) or 16 bytes per block. */
-typedef struct { const orc_options *options; int format; } s3tc_job_t;
+typedef struct
+{
+    const orc_options *options;
+    int format;
+    float *colorErr; /* NULL, or one float per block (BC2, BC3) */
+    float *alphaErr; /* NULL, or one float per block and interpolated channel (BC3, BC4: 1; BC5: 2) */
+} s3tc_job_t;
 
-static void s3tc_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp)
+static void s3tc_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)b;
     const s3tc_job_t *job = (const s3tc_job_t *)a;
     const orc_options *o = job->options;
     if (job->format == 2 || job->format == 3)
-        s3tc_pack_rgb_group(in, out + 8, 16, o, rcp, 0);
+        s3tc_pack_rgb_group(in, out + 8, 16, o, rcp, 0, job->colorErr ? job->colorErr + group * 8 : NULL);
+    const int alphaChannels = job->format >= 6 ? 2 : 1;
     for (int blk = 0; blk < 8; blk++)
     {
+        float *aerr = job->alphaErr ? job->alphaErr + (group * 8 + (size_t)blk) * (size_t)alphaChannels : NULL;
         const uint8_t *src = in + blk * 64;
         uint8_t biased[64];
         if (job->format == 5 || job->format == 7)
@@ -273,22 +284,23 @@ static void s3tc_group_thunk(const uint8_t *in, uint8_t *out, const void *a, con
             s3tc_explicit_alpha(src, 3, out + blk * 16);
             break;
         case 3:
-            s3tc_interpolated_alpha(src, 3, out + blk * 16, o->flags, 0, o->seedPoints, o->refineRoundsIIC, rcp);
+            s3tc_interpolated_alpha(src, 3, out + blk * 16, o->flags, 0, o->seedPoints, o->refineRoundsIIC, rcp, aerr);
             break;
         case 4:
         case 5:
-            s3tc_interpolated_alpha(src, 0, out + blk * 8, o->flags, job->format == 5, o->seedPoints, o->refineRoundsIIC, rcp);
+            s3tc_interpolated_alpha(src, 0, out + blk * 8, o->flags, job->format == 5, o->seedPoints, o->refineRoundsIIC, rcp, aerr);
             break;
         default:
-            s3tc_interpolated_alpha(src, 0, out + blk * 16, o->flags, job->format == 7, o->seedPoints, o->refineRoundsIIC, rcp);
-            s3tc_interpolated_alpha(src, 1, out + blk * 16 + 8, o->flags, job->format == 7, o->seedPoints, o->refineRoundsIIC, rcp);
+            s3tc_interpolated_alpha(src, 0, out + blk * 16, o->flags, job->format == 7, o->seedPoints, o->refineRoundsIIC, rcp, aerr);
+            s3tc_interpolated_alpha(src, 1, out + blk * 16 + 8, o->flags, job->format == 7, o->seedPoints, o->refineRoundsIIC, rcp,
+                                    aerr ? aerr + 1 : NULL);
             break;
         }
     }
 }
 
-int orc_encode_s3tc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
-                    const float *rcp17, int threads)
+static int s3tc_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
+                       const float *rcp17, int threads, float *colorErr, float *alphaErr)
 {
     if (numBlocks % 8 != 0 || format < 2 || format > 7)
         return -1;
@@ -298,8 +310,14 @@ int orc_encode_s3tc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const
         orc_probe_rcp(probed);
         rcp17 = probed;
     }
-    s3tc_job_t job = {options, format};
+    s3tc_job_t job = {options, format, colorErr, format == 2 ? NULL : alphaErr};
     const size_t outPer = (format == 4 || format == 5) ? 8 : 16;
     run_groups(s3tc_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * outPer, &job, NULL, rcp17, threads);
     return 0;
+}
+
+int orc_encode_s3tc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
+                    const float *rcp17, int threads)
+{
+    return s3tc_encode(out, blocks, numBlocks, options, format, rcp17, threads, NULL, NULL);
 }

@@ -284,6 +284,72 @@ class OracleLib:
             raise RuntimeError("orc_encode_s3tc rc=%d" % rc)
         return out.reshape(n, per)
 
+    # ---- the same encodes, also returning the encoder's final per-block error (the score of the emitted candidate) ----
+    @staticmethod
+    def _rcp_ptr(rcp):
+        if rcp is None:
+            return None, None
+        rcp = np.ascontiguousarray(rcp, np.float32)
+        assert rcp.size == 17
+        return rcp, rcp.ctypes.data_as(ctypes.c_void_p)
+
+    def encode_etc2_err(self, blocks, options, mode, threads=1, alloc_options=None):
+        """encode_etc2 plus the errors: returns (packed, color_err, alpha_err).  color_err: (N,) float32 for modes 0, 1, 3, 4,
+        else None; alpha_err: (N,) uint32 EAC error for modes 1, 2, else None."""
+        blocks, pb = _u8(blocks)
+        n = blocks.size // 64
+        assert n % 8 == 0
+        per = 16 if mode == 1 else 8
+        out = np.zeros(n * per, np.uint8)
+        ao = options if alloc_options is None else alloc_options
+        cerr = np.full(n, np.nan, np.float32) if mode != 2 else None
+        aerr = np.full(n, 0xFFFFFFFF, np.uint32) if mode in (1, 2) else None
+        self.lib.orc_encode_etc2_err.restype = ctypes.c_int
+        rc = self.lib.orc_encode_etc2_err(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                          options.ctypes.data_as(ctypes.c_void_p), ao.ctypes.data_as(ctypes.c_void_p),
+                                          ctypes.c_int(mode), ctypes.c_int(threads),
+                                          cerr.ctypes.data_as(ctypes.c_void_p) if cerr is not None else None,
+                                          aerr.ctypes.data_as(ctypes.c_void_p) if aerr is not None else None)
+        if rc != 0:
+            raise RuntimeError("orc_encode_etc2_err rc=%d" % rc)
+        return out.reshape(n, per), cerr, aerr
+
+    def encode_s3tc_err(self, blocks, options, fmt, rcp=None, threads=1):
+        """encode_s3tc plus the errors: returns (packed, color_err, alpha_err).  color_err: (N,) float32 for BC2 / BC3, else
+        None; alpha_err: (N, C) float32 per interpolated channel (BC3, BC4: C = 1; BC5: C = 2), None for BC2."""
+        blocks, pb = _u8(blocks)
+        n = blocks.size // 64
+        assert n % 8 == 0
+        per = 8 if fmt in (4, 5) else 16
+        out = np.zeros(n * per, np.uint8)
+        rcp, rcp_p = self._rcp_ptr(rcp)
+        cerr = np.full(n, np.nan, np.float32) if fmt in (2, 3) else None
+        aerr = np.full((n, 2 if fmt >= 6 else 1), np.nan, np.float32) if fmt != 2 else None
+        self.lib.orc_encode_s3tc_err.restype = ctypes.c_int
+        rc = self.lib.orc_encode_s3tc_err(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                          options.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(fmt), rcp_p, ctypes.c_int(threads),
+                                          cerr.ctypes.data_as(ctypes.c_void_p) if cerr is not None else None,
+                                          aerr.ctypes.data_as(ctypes.c_void_p) if aerr is not None else None)
+        if rc != 0:
+            raise RuntimeError("orc_encode_s3tc_err rc=%d" % rc)
+        return out.reshape(n, per), cerr, aerr
+
+    def encode_bc1_err(self, blocks, options, rcp=None, threads=1):
+        """encode_bc1 plus the error: returns (packed, err) with err (N,) float32."""
+        blocks, pb = _u8(blocks)
+        n = blocks.size // 64
+        assert n % 8 == 0
+        out = np.zeros(n * 8, np.uint8)
+        rcp, rcp_p = self._rcp_ptr(rcp)
+        err = np.full(n, np.nan, np.float32)
+        self.lib.orc_encode_bc1_err.restype = ctypes.c_int
+        rc = self.lib.orc_encode_bc1_err(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                         options.ctypes.data_as(ctypes.c_void_p), rcp_p, ctypes.c_int(threads),
+                                         err.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise RuntimeError("orc_encode_bc1_err rc=%d" % rc)
+        return out.reshape(n, 8), err
+
     def encode_eac11(self, blocks_s16, signed=False):
         b = np.ascontiguousarray(blocks_s16, dtype=np.int16)
         n = b.size // 16

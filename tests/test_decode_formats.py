@@ -3,7 +3,8 @@
 CPU: the numpy restatement (texture_decode_ref.py) against Pillow's DDS decoder (tests/golden/bcn_pillow.npz), the coverage
 of the seeded random blocks the GPU tests use, the cvttmi_error_totals layout and cvttmi_psnr.
 GPU: every decoder against the restatement, host and device forms, the measure's per-block values and totals (exact; BC6H
-in the documented float order), determinism across streams, the image form, error codes and the packer's -metrics."""
+in the documented float order), determinism across streams, the image form, error codes and the packer's -metrics.
+The restatement's own independent anchor is tests/test_encoder_error_anchor.py: the final per-block error of the encoder."""
 import ctypes
 import io
 import os

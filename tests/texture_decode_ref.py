@@ -12,6 +12,7 @@ reference encoder scores its candidates with:
                    (ConvectionKernels_Util.cpp:47-60) -- -128 reads as -127, high terminal 254 in the biased domain
   ETC1/ETC2/EAC    integer-exact: individual, differential, T, H, planar, punch-through (ETC.cpp emitters 2414-2622);
                    EAC 8-bit and R11 as QuantizeETC2Alpha reconstructs (ETC.cpp:2366-2404, input ranges 2087-2113)
+  (tests/test_encoder_error_anchor.py holds all of the above but R11 to the encoder's own final per-block error, exactly)
   BC7 / BC6H       not restated here: the reference's decoders (oracle/_ref) and tests/golden/decode.npz cover them
 
 Layouts ("a decoder writes what its encoder reads"): PixelBlockU8 (N,16,4) uint8; BC4S/BC5S PixelBlockS8 (N,16,4) int8;
