@@ -152,7 +152,22 @@ int cvttmi_host_unregister(cvttmi_context *ctx, void *ptr);
  * EAC, decode, tiling) are simply queued on the stream given.  A mutex serialises the host side of EVERY call on a
  * context, so any stream / thread mix is safe on one context; it is not concurrent: use one context per stream (or per
  * worker thread, the reference's caller model, etc2packer.cpp:215-281) to overlap independent jobs.  (EncodeBC6H keeps its
- * whole search state on the chip since round 4: no work buffer, no ordering between its calls.) ---- */
+ * whole search state on the chip since round 4: no work buffer, no ordering between its calls.)
+ *
+ * Buffers.  Every pointer may point into the middle of a larger allocation (a mip level, a shard, blocks [a, b) of a batch): a
+ * call reads its inputs only, and writes exactly numBlocks x bytesPerBlock bytes from d_out on (the tiling calls: the block
+ * counts documented with them; the measure: numBlocks per-block values and the 80 bytes of the totals) -- never a byte before
+ * or behind, whatever the launch rounds its grid up to.  Input and output must not overlap.
+ * Alignment of DEVICE pointers: one element of what the pointer points at, or 16 bytes where the element is larger.  That is
+ *   blocks in and out (PixelBlockU8 / S8 / F16 / ScalarS16, packed and decoded blocks): min(bytes per block, 16), i.e. 8 for
+ *     the 8-byte formats (BC1, BC4, ETC1, ETC2 RGB / punch-through, EAC alpha, R11) and 16 for everything else;
+ *   images: the texel size (4 bytes RGBA8, 8 bytes RGBA16F), rowPitchBytes a multiple of it;
+ *   per-block error values: 4 bytes;  cvttmi_error_totals: 8 bytes.
+ * These are the widest accesses the kernels make through a caller's pointer (16-byte loads of PixelBlocks and 16-byte packed
+ * blocks, 8-byte stores of 8-byte blocks, one texel of an image, one uint32 / float, the 64-bit fields of the totals).  A
+ * device pointer that breaks the rule is rejected with CVTTMI_E_INVALID before anything is queued; nothing is written.
+ * HOST pointers (the entry points without _device) need no alignment at all, like the reference's byte arrays: pageable and
+ * misaligned page-locked buffers are staged, block-aligned page-locked ones are transferred in place. ---- */
 
 /* replaces cvtt::Kernels::EncodeBC7 (ConvectionKernels_API.cpp:41-54): numBlocks * 64 B
  * of PixelBlockU8 in, numBlocks * 16 B out. */
@@ -342,7 +357,9 @@ typedef struct cvttmi_error_totals
 int cvttmi_decode_device(cvttmi_context *ctx, int format, void *d_out, const void *d_bc, size_t numBlocks, void *hipStream);
 int cvttmi_decode(cvttmi_context *ctx, int format, void *out, const uint8_t *bc, size_t numBlocks);
 /* d_source: numBlocks blocks of the encoder's input layout.  d_blockError: NULL, or numBlocks uint32 (float for BC6H).
- * d_totals: device memory (the host form: host memory) the totals are written to. */
+ * d_totals: device memory (the host form: host memory) the totals are written to.  A call OVERWRITES all 80 bytes of the
+ * totals (they need no initial value, and nothing accumulates from one call to the next) and every one of the numBlocks
+ * per-block values. */
 int cvttmi_measure_error_device(cvttmi_context *ctx, int format, const void *d_bc, const void *d_source, size_t numBlocks,
                                 void *d_blockError, cvttmi_error_totals *d_totals, void *hipStream);
 int cvttmi_measure_error(cvttmi_context *ctx, int format, const uint8_t *bc, const void *source, size_t numBlocks,

@@ -259,7 +259,8 @@ def test_second_launch_hand_over_is_invisible(gpu_ctx, oracle_lib, monkeypatch):
     # A punch-through encode between two encodes with a hand-over, on one context.  The two hand-over counters alternate,
     # each encode's first kernel clearing the next one's; the punch-through kernel clears none, so it gets no slots, and
     # the third encode must not start on the first one's records.  (Equal block counts: stale records would still point
-    # inside the buffers.)
+    # inside the buffers; test_buffer_contract.py::test_stale_hand_over_records_stay_inside_a_smaller_encode follows a
+    # large encode with a small one into a guarded buffer.)
     import ctypes
     for k in ("CVTTMI_BC7_HARD_MIN", "CVTTMI_BC7_HARD_CAP", "CVTTMI_BC7_HARD_DIV"):
         monkeypatch.delenv(k, raising=False)
