@@ -197,6 +197,7 @@ _EXPORTS = (
     "cvttmi_multi_context", "cvttmi_multi_last_shard", "cvttmi_multi_set_rcp_table", "cvttmi_multi_set_exhaustive", "cvttmi_multi_encode", "cvttmi_multi_encode_device",
     "cvttmi_encode_bc7_multi", "cvttmi_encode_bc1_multi", "cvttmi_encode_bc6h_multi", "cvttmi_encode_etc2_rgba_multi",
     "cvttmi_dropin_set_devices",
+    "cvttmi_format_info", "cvttmi_encode_device", "cvttmi_encode",
 )
 
 _lib = None
@@ -262,41 +263,25 @@ def load_library():
     lib.cvttmi_destroy.argtypes = [ctypes.c_void_p]
     lib.cvttmi_set_rcp_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.cvttmi_get_rcp_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                      ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_bc1_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                             ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_bc1.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.cvttmi_encode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.cvttmi_encode_bc6h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                       ctypes.c_void_p, ctypes.c_int]
-    for n in ("cvttmi_encode_etc2", "cvttmi_encode_etc2_rgba", "cvttmi_encode_etc2_alpha", "cvttmi_encode_etc1",
-              "cvttmi_encode_etc2_punchthrough_alpha"):
-        getattr(lib, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        getattr(lib, n + "_device").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                 ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_etc2_with_data.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    lib.cvttmi_encode_etc2_with_data_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_int, ctypes.c_void_p]
+    P, N, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    # the encoders: the generic entry, and the named ones by signature family -- (ctx, out, blocks, numBlocks, options, extra...),
+    # the _device forms with a stream behind
+    lib.cvttmi_format_info.argtypes = [I, ctypes.POINTER(N), ctypes.POINTER(N), ctypes.POINTER(ctypes.c_uint32)]
+    lib.cvttmi_encode.argtypes = [P, I, P, P, N, P, P, P]
+    lib.cvttmi_encode_device.argtypes = [P, I, P, P, N, P, P, P, P]
+    for names, extra in ((("bc1", "bc2", "bc3", "etc1", "etc2", "etc2_rgba", "etc2_alpha", "etc2_punchthrough_alpha"), []),
+                         (("bc7",), [P]), (("bc4", "bc5", "bc6h"), [I]), (("etc2_with_data",), [P, I])):
+        for n in names:
+            getattr(lib, "cvttmi_encode_" + n).argtypes = [P, P, P, N, P] + extra
+            getattr(lib, "cvttmi_encode_" + n + "_device").argtypes = [P, P, P, N, P] + extra + [P]
+    lib.cvttmi_encode_etc2_alpha11.argtypes = [P, P, P, N, I, P]
+    lib.cvttmi_encode_etc2_alpha11_device.argtypes = [P, P, P, N, I, P, P]
     lib.cvttmi_tiled_block_count.restype = ctypes.c_size_t
     lib.cvttmi_tiled_block_count.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     lib.cvttmi_tile_image_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     lib.cvttmi_compact_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                                ctypes.c_uint32, ctypes.c_void_p]
-    for n in ("cvttmi_encode_bc2", "cvttmi_encode_bc3"):
-        getattr(lib, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        getattr(lib, n + "_device").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-    for n in ("cvttmi_encode_bc4", "cvttmi_encode_bc5"):
-        getattr(lib, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
-        getattr(lib, n + "_device").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.c_void_p]
-    lib.cvttmi_encode_etc2_alpha11_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
-                                                      ctypes.c_void_p, ctypes.c_void_p]
-    lib.cvttmi_encode_etc2_alpha11.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     lib.cvttmi_decode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
@@ -560,185 +545,117 @@ class Context:
         self._check(self._lib.cvttmi_timing_read(self._h, ctypes.byref(ms), ctypes.byref(n)), "timing_read")
         return ms.value, n.value
 
+    # -- every encoder, by format name (cvttmi_encode / cvttmi_encode_device); the methods named after the reference's calls follow --
+    def encode(self, fmt, blocks, options=None, plan=None, out=None, stream=None, compression_data=None):
+        """Batched cvtt::Kernels::Encode* of format ``fmt`` (a name of TEXTURE_FORMATS).  ``blocks``: N blocks (a multiple of 8)
+        in the layout the format's encoder reads -- (N,16,4) uint8 PixelBlockU8, int8 PixelBlockS8 for BC4S / BC5S, 2-byte half
+        bit patterns for BC6H, (N,16) int16 PixelBlockScalarS16 for R11 -- as a numpy array (host path) or a tensor on this
+        context's GPU (device path, asynchronous on ``stream`` / the current torch stream) -> (N, bytes per block) uint8.
+        plan: BC7 only (None = BC7EncodingPlan()).  compression_data: ETC2 RGB / RGBA / punch-through only -- what AllocETC2Data
+        returned, or the Options it was given: the chroma axes of the sector split belong to those (reference
+        ConvectionKernels_ETC.cpp:3117-3145), the rest to `options`; None = allocated with `options`."""
+        fid, out_bytes, in_bytes, _ = self._texture_format(fmt)
+        options = options if options is not None else Options()
+        if fmt == "bc7" and plan is None:
+            plan = BC7EncodingPlan()
+        ao = compression_data.alloc_options if isinstance(compression_data, ETC2CompressionData) else compression_data
+        planp = ctypes.addressof(plan) if plan is not None else None
+        aop = ctypes.addressof(ao) if ao is not None else None
+        what = "encode(%s)" % fmt
+        if isinstance(blocks, np.ndarray):
+            # values are converted where callers hand over plain integers (BC7: uint8, R11: int16); every other array is taken
+            # by its bytes (int8 for the signed formats, any 2-byte dtype for BC6H)
+            b = np.ascontiguousarray(blocks, {"bc7": np.uint8, "r11u": np.int16, "r11s": np.int16}.get(fmt))
+            n = b.nbytes // in_bytes
+            if b.nbytes % in_bytes or n % NumParallelBlocks:
+                raise CvttError("blocks must hold a multiple of 8 pixel blocks of %d bytes" % in_bytes)
+            res = self._host_out(out, n, out_bytes)
+            with self._host_lock:
+                self._check(self._lib.cvttmi_encode(self._h, fid, res.ctypes.data, b.ctypes.data, n, ctypes.addressof(options), planp, aop), what)
+            return res
+        b = self._device_in(blocks)
+        if fmt == "bc7" and str(b.dtype) != "torch.uint8":
+            raise CvttError("blocks must be a numpy uint8 array or a CUDA uint8 tensor")
+        nbytes = b.numel() * b.element_size()
+        n = nbytes // in_bytes
+        if nbytes % in_bytes or n % NumParallelBlocks:
+            raise CvttError("blocks must hold a multiple of 8 pixel blocks of %d bytes" % in_bytes)
+        res = self._device_out(out, n, out_bytes, b)
+        stream = self._stream(stream, b.device)
+        self._check(self._lib.cvttmi_encode_device(self._h, fid, res.data_ptr(), b.data_ptr(), n, ctypes.addressof(options), planp, aop,
+                                                   ctypes.c_void_p(stream)), what)
+        return res
+
     # -- BC7 --
     def encode_bc7(self, blocks, options=None, plan=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC7.  ``blocks``: (N,16,4) uint8 numpy array (host
         path) or a torch uint8 tensor on this context's GPU (device path, asynchronous on
         ``stream`` / the current torch stream).  N must be a multiple of 8."""
-        options = options if options is not None else Options()
-        plan = plan if plan is not None else BC7EncodingPlan()
-        if isinstance(blocks, np.ndarray):
-            b = np.ascontiguousarray(blocks, np.uint8)
-            n = b.size // 64
-            if b.size % 64 or n % NumParallelBlocks:
-                raise CvttError("blocks must hold a multiple of 8 PixelBlockU8")
-            res = self._host_out(out, n, 16)
-            with self._host_lock:
-                self._check(self._lib.cvttmi_encode_bc7(self._h, res.ctypes.data, b.ctypes.data, n,
-                                                        ctypes.addressof(options), ctypes.addressof(plan)), "encode_bc7")
-            return res
-        import torch
-        b = self._device_in(blocks)
-        if b.dtype != torch.uint8:
-            raise CvttError("blocks must be a numpy uint8 array or a CUDA uint8 tensor")
-        n = b.numel() // 64
-        if b.numel() % 64 or n % NumParallelBlocks:
-            raise CvttError("blocks must hold a multiple of 8 PixelBlockU8")
-        res = self._device_out(out, n, 16, b)
-        stream = self._stream(stream, b.device)
-        self._check(self._lib.cvttmi_encode_bc7_device(self._h, res.data_ptr(), b.data_ptr(), n,
-                                                       ctypes.addressof(options), ctypes.addressof(plan),
-                                                       ctypes.c_void_p(stream)), "encode_bc7_device")
-        return res
-
-
-    # -- generic helper for the formats without a plan argument --
-    def _encode_simple(self, host_fn, dev_fn, what, blocks, options, out, stream, in_bytes, out_bytes):
-        options = options if options is not None else Options()
-        if isinstance(blocks, np.ndarray):
-            b = np.ascontiguousarray(blocks)
-            n = b.nbytes // in_bytes
-            if b.nbytes % in_bytes or n % NumParallelBlocks:
-                raise CvttError("blocks must hold a multiple of 8 pixel blocks")
-            res = self._host_out(out, n, out_bytes)
-            with self._host_lock:
-                self._check(host_fn(self._h, res.ctypes.data, b.ctypes.data, n, ctypes.addressof(options)), what)
-            return res
-        b = self._device_in(blocks)
-        nbytes = b.numel() * b.element_size()
-        n = nbytes // in_bytes
-        if nbytes % in_bytes or n % NumParallelBlocks:
-            raise CvttError("blocks must hold a multiple of 8 pixel blocks")
-        res = self._device_out(out, n, out_bytes, b)
-        stream = self._stream(stream, b.device)
-        self._check(dev_fn(self._h, res.data_ptr(), b.data_ptr(), n, ctypes.addressof(options), ctypes.c_void_p(stream)), what)
-        return res
+        return self.encode("bc7", blocks, options, plan, out, stream)
 
     # -- BC1 --
     def encode_bc1(self, blocks, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC1: (N,16,4) uint8 -> (N,8) uint8."""
-        return self._encode_simple(self._lib.cvttmi_encode_bc1, self._lib.cvttmi_encode_bc1_device, "encode_bc1",
-                                   blocks, options, out, stream, 64, 8)
-
+        return self.encode("bc1", blocks, options, None, out, stream)
 
     # -- BC2 / BC3 / BC4 / BC5 --
     def encode_bc2(self, blocks, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC2: (N,16,4) uint8 -> (N,16) uint8 [explicit alpha | colour]."""
-        return self._encode_simple(self._lib.cvttmi_encode_bc2, self._lib.cvttmi_encode_bc2_device, "encode_bc2", blocks, options, out, stream, 64, 16)
+        return self.encode("bc2", blocks, options, None, out, stream)
 
     def encode_bc3(self, blocks, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC3: (N,16,4) uint8 -> (N,16) uint8 [interpolated alpha | colour]."""
-        return self._encode_simple(self._lib.cvttmi_encode_bc3, self._lib.cvttmi_encode_bc3_device, "encode_bc3", blocks, options, out, stream, 64, 16)
+        return self.encode("bc3", blocks, options, None, out, stream)
 
     def encode_bc4(self, blocks, options=None, signed=False, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC4U / EncodeBC4S (red channel; signed: int8 PixelBlockS8): -> (N,8) uint8."""
-        sg = 1 if signed else 0
-        host = lambda h, o, b, n, opt: self._lib.cvttmi_encode_bc4(h, o, b, n, opt, sg)
-        dev = lambda h, o, b, n, opt, st: self._lib.cvttmi_encode_bc4_device(h, o, b, n, opt, sg, st)
-        if isinstance(blocks, np.ndarray) and blocks.dtype == np.int8:
-            blocks = blocks.view(np.uint8)
-        return self._encode_simple(host, dev, "encode_bc4", blocks, options, out, stream, 64, 8)
+        return self.encode("bc4s" if signed else "bc4u", blocks, options, None, out, stream)
 
     def encode_bc5(self, blocks, options=None, signed=False, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC5U / EncodeBC5S (red, green): -> (N,16) uint8."""
-        sg = 1 if signed else 0
-        host = lambda h, o, b, n, opt: self._lib.cvttmi_encode_bc5(h, o, b, n, opt, sg)
-        dev = lambda h, o, b, n, opt, st: self._lib.cvttmi_encode_bc5_device(h, o, b, n, opt, sg, st)
-        if isinstance(blocks, np.ndarray) and blocks.dtype == np.int8:
-            blocks = blocks.view(np.uint8)
-        return self._encode_simple(host, dev, "encode_bc5", blocks, options, out, stream, 64, 16)
+        return self.encode("bc5s" if signed else "bc5u", blocks, options, None, out, stream)
 
     # -- BC6H --
     def encode_bc6h(self, blocks, options=None, signed=False, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeBC6HU / EncodeBC6HS: (N,16,4) half bit patterns (int16 /
         uint16 / float16 numpy array, or a CUDA tensor of 2-byte elements) -> (N,16) uint8."""
-        sg = 1 if signed else 0
-        host = lambda h, o, b, n, opt: self._lib.cvttmi_encode_bc6h(h, o, b, n, opt, sg)
-        dev = lambda h, o, b, n, opt, st: self._lib.cvttmi_encode_bc6h_device(h, o, b, n, opt, sg, st)
-        return self._encode_simple(host, dev, "encode_bc6h", blocks, options, out, stream, 128, 16)
-
+        return self.encode("bc6hs" if signed else "bc6hu", blocks, options, None, out, stream)
 
     # -- ETC1 / ETC2 --
     def encode_etc1(self, blocks, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeETC1: (N,16,4) uint8 -> (N,8) uint8."""
-        return self._encode_simple(self._lib.cvttmi_encode_etc1, self._lib.cvttmi_encode_etc1_device, "encode_etc1",
-                                   blocks, options, out, stream, 64, 8)
-
-    def _encode_etc2_kind(self, kind, what, blocks, options, out, stream, out_bytes, compression_data):
-        """The three calls that take the reference's ETC2CompressionData: the chroma axes of the sector split belong to the
-        Options AllocETC2Data was called with (reference ConvectionKernels_ETC.cpp:3117-3145), the rest to `options`."""
-        ao = None
-        if compression_data is not None:
-            ao = compression_data.alloc_options if isinstance(compression_data, ETC2CompressionData) else compression_data
-        aop = ctypes.byref(ao) if ao is not None else None
-        host = lambda h, o, b, n, opt: self._lib.cvttmi_encode_etc2_with_data(h, o, b, n, opt, aop, kind)
-        dev = lambda h, o, b, n, opt, st: self._lib.cvttmi_encode_etc2_with_data_device(h, o, b, n, opt, aop, kind, st)
-        return self._encode_simple(host, dev, what, blocks, options, out, stream, 64, out_bytes)
+        return self.encode("etc1", blocks, options, None, out, stream)
 
     def encode_etc2(self, blocks, options=None, out=None, stream=None, compression_data=None):
         """Batched cvtt::Kernels::EncodeETC2 (RGB): (N,16,4) uint8 -> (N,8) uint8.  compression_data: what AllocETC2Data
         returned (or the Options it was given); None = allocated with `options`."""
-        return self._encode_etc2_kind(0, "encode_etc2", blocks, options, out, stream, 8, compression_data)
+        return self.encode("etc2", blocks, options, None, out, stream, compression_data)
 
     def encode_etc2_punchthrough_alpha(self, blocks, options=None, out=None, stream=None, compression_data=None):
         """Batched cvtt::Kernels::EncodeETC2PunchthroughAlpha: (N,16,4) uint8 -> (N,8) uint8 (RGB8A1 blocks; a pixel is
         transparent when its alpha is below floor(clamp(options.threshold, 0, 1) * 255 + 1))."""
-        return self._encode_etc2_kind(4, "encode_etc2_punchthrough_alpha", blocks, options, out, stream, 8, compression_data)
+        return self.encode("etc2punchthrough", blocks, options, None, out, stream, compression_data)
 
     def encode_etc2_rgba(self, blocks, options=None, out=None, stream=None, compression_data=None):
         """Batched cvtt::Kernels::EncodeETC2RGBA: (N,16,4) uint8 -> (N,16) uint8 = [EAC alpha | colour]."""
-        return self._encode_etc2_kind(1, "encode_etc2_rgba", blocks, options, out, stream, 16, compression_data)
+        return self.encode("etc2rgba", blocks, options, None, out, stream, compression_data)
 
     def encode_etc2_alpha(self, blocks, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeETC2Alpha (EAC 8-bit): (N,16,4) uint8 -> (N,8) uint8."""
-        return self._encode_simple(self._lib.cvttmi_encode_etc2_alpha, self._lib.cvttmi_encode_etc2_alpha_device,
-                                   "encode_etc2_alpha", blocks, options, out, stream, 64, 8)
-
+        return self.encode("eac", blocks, options, None, out, stream)
 
     def encode_etc2_alpha11(self, blocks, signed=False, options=None, out=None, stream=None):
         """Batched cvtt::Kernels::EncodeETC2Alpha11 (EAC R11): (N,16) int16 PixelBlockScalarS16 -> (N,8) uint8."""
-        sg = 1 if signed else 0
-        host = lambda h, o, b, n, opt: self._lib.cvttmi_encode_etc2_alpha11(h, o, b, n, sg, opt)
-        dev = lambda h, o, b, n, opt, st: self._lib.cvttmi_encode_etc2_alpha11_device(h, o, b, n, sg, opt, st)
-        if isinstance(blocks, np.ndarray):
-            blocks = np.ascontiguousarray(blocks, np.int16)
-        return self._encode_simple(host, dev, "encode_etc2_alpha11", blocks, options, out, stream, 32, 8)
+        return self.encode("r11s" if signed else "r11u", blocks, options, None, out, stream)
 
     # -- decoders (cvtt::Kernels::DecodeBC7 / DecodeBC6HU / DecodeBC6HS) --
-    def _decode(self, packed, fmt, stream):
-        hdr = fmt != "bc7"
-        sg = 1 if fmt == "bc6hs" else 0
-        if isinstance(packed, np.ndarray):
-            b = np.ascontiguousarray(packed, np.uint8)
-            n = b.size // 16
-            if b.size % 16 or n % NumParallelBlocks:
-                raise CvttError("packed must hold a multiple of 8 16-byte blocks")
-            res = np.empty((n, 16, 4), np.int16 if hdr else np.uint8)
-            with self._host_lock:
-                rc = (self._lib.cvttmi_decode_bc6h(self._h, res.ctypes.data, b.ctypes.data, n, sg) if hdr
-                      else self._lib.cvttmi_decode_bc7(self._h, res.ctypes.data, b.ctypes.data, n))
-            self._check(rc, "decode")
-            return res
-        import torch
-        b = self._device_in(packed, "packed")
-        nbytes = b.numel() * b.element_size()
-        n = nbytes // 16
-        if nbytes % 16 or n % NumParallelBlocks:
-            raise CvttError("packed must hold a multiple of 8 16-byte blocks")
-        res = torch.empty((n, 16, 4), dtype=torch.int16 if hdr else torch.uint8, device=b.device)
-        stream = self._stream(stream, b.device)
-        rc = (self._lib.cvttmi_decode_bc6h_device(self._h, res.data_ptr(), b.data_ptr(), n, sg, ctypes.c_void_p(stream)) if hdr
-              else self._lib.cvttmi_decode_bc7_device(self._h, res.data_ptr(), b.data_ptr(), n, ctypes.c_void_p(stream)))
-        self._check(rc, "decode")
-        return res
-
     def decode_bc7(self, packed, stream=None):
         """(N,16) uint8 packed BC7 blocks (numpy or CUDA tensor) -> (N,16,4) uint8 PixelBlockU8"""
-        return self._decode(packed, "bc7", stream)
+        return self.decode("bc7", packed, stream)
 
     def decode_bc6h(self, packed, signed=False, stream=None):
         """(N,16) uint8 packed BC6H blocks -> (N,16,4) int16 half bit patterns (alpha = 0x3C00)"""
-        return self._decode(packed, "bc6hs" if signed else "bc6hu", stream)
+        return self.decode("bc6hs" if signed else "bc6hu", packed, stream)
 
     def psnr_bc7(self, blocks, packed):
         """PSNR (dB, over the four channels) of the decoded `packed` blocks against the source PixelBlockU8 tensor, on the device"""
@@ -905,21 +822,9 @@ class Context:
         "bc6hu", "bc6hs" from an (H,W,4) half-float image."""
         h, w = int(image.shape[0]), int(image.shape[1])
         blocks = self.tile_image(image, stream)
-        simple = {"bc1": self.encode_bc1, "bc2": self.encode_bc2, "bc3": self.encode_bc3, "etc1": self.encode_etc1,
-                  "etc2": self.encode_etc2, "etc2rgb": self.encode_etc2, "etc2rgba": self.encode_etc2_rgba, "eac": self.encode_etc2_alpha,
-                  "etc2punchthrough": self.encode_etc2_punchthrough_alpha}
-        if fmt == "bc7":
-            packed = self.encode_bc7(blocks, options, plan, stream=stream)
-        elif fmt in simple:
-            packed = simple[fmt](blocks, options, stream=stream)
-        elif fmt in ("bc4u", "bc4s"):
-            packed = self.encode_bc4(blocks, options, signed=(fmt == "bc4s"), stream=stream)
-        elif fmt in ("bc5u", "bc5s"):
-            packed = self.encode_bc5(blocks, options, signed=(fmt == "bc5s"), stream=stream)
-        elif fmt in ("bc6hu", "bc6hs"):
-            packed = self.encode_bc6h(blocks, options, signed=(fmt == "bc6hs"), stream=stream)
-        else:
+        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
+        packed = self.encode(fmt, blocks, options, plan, stream=stream)
         return packed if w % 32 == 0 else self.compact_rows(packed, w, h, stream)
 
 
@@ -939,8 +844,9 @@ def shard_block_rows(block_rows, blocks_per_row, rank, world):
 
 class MultiContext:
     """One job on several devices behind the C ABI (cvttmi_multi_*, csrc/multi.cpp): one context per entry of `devices` (a
-    device may appear more than once), block-row shards, packed output straight into the caller's buffer.  Host arrays only."""
-    FORMATS = {"bc7": (0, 64, 16), "bc1": (1, 64, 8), "bc6hu": (2, 128, 16), "bc6hs": (3, 128, 16), "etc2": (4, 64, 8), "etc2rgba": (5, 64, 16)}
+    device may appear more than once), block-row shards, packed output straight into the caller's buffer.  Host arrays only.
+    Every format with an encoder: the names of TEXTURE_FORMATS."""
+    FORMATS = {name: (fid, tex, bpb) for name, (fid, bpb, tex, _) in TEXTURE_FORMATS.items()}  # name -> (id, in bytes, out bytes)
 
     def __init__(self, devices):
         self._lib = load_library()

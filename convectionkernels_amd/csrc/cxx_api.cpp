@@ -72,7 +72,7 @@ namespace
     // ---- coalescing of concurrent one-group calls (coalescer.h) ----
     struct CallKey
     {
-        int kind;                 // which entry point (and its integer argument)
+        int kind;                 // the format: CVTTMI_FMT_*
         cvttmi_options options;
         cvttmi_options allocOptions; // ETC2: the Options of AllocETC2Data
         bool hasAlloc;
@@ -100,33 +100,10 @@ namespace
         return k;
     }
 
-    enum Kind { K_BC7, K_BC1, K_BC2, K_BC3, K_BC4U, K_BC4S, K_BC5U, K_BC5S, K_BC6HU, K_BC6HS, K_ETC1, K_ETC2, K_ETC2RGBA, K_ETC2PT, K_ETC2A, K_A11U, K_A11S };
     // encode `n` contiguous blocks with the given key on `ctx`
     int encodeBatch(cvttmi_context *ctx, const CallKey &k, uint8_t *out, const uint8_t *in, size_t n)
     {
-        const cvttmi_options *o = &k.options;
-        const cvttmi_options *ao = k.hasAlloc ? &k.allocOptions : NULL;
-        switch (k.kind)
-        {
-        case K_BC7: return cvttmi_encode_bc7(ctx, out, in, n, o, &k.plan);
-        case K_BC1: return cvttmi_encode_bc1(ctx, out, in, n, o);
-        case K_BC2: return cvttmi_encode_bc2(ctx, out, in, n, o);
-        case K_BC3: return cvttmi_encode_bc3(ctx, out, in, n, o);
-        case K_BC4U: return cvttmi_encode_bc4(ctx, out, in, n, o, 0);
-        case K_BC4S: return cvttmi_encode_bc4(ctx, out, in, n, o, 1);
-        case K_BC5U: return cvttmi_encode_bc5(ctx, out, in, n, o, 0);
-        case K_BC5S: return cvttmi_encode_bc5(ctx, out, in, n, o, 1);
-        case K_BC6HU: return cvttmi_encode_bc6h(ctx, out, in, n, o, 0);
-        case K_BC6HS: return cvttmi_encode_bc6h(ctx, out, in, n, o, 1);
-        case K_ETC1: return cvttmi_encode_etc1(ctx, out, in, n, o);
-        case K_ETC2: return cvttmi_encode_etc2_with_data(ctx, out, in, n, o, ao, CVTTMI_ETC2_RGB);
-        case K_ETC2RGBA: return cvttmi_encode_etc2_with_data(ctx, out, in, n, o, ao, CVTTMI_ETC2_RGBA);
-        case K_ETC2PT: return cvttmi_encode_etc2_with_data(ctx, out, in, n, o, ao, CVTTMI_ETC2_PUNCHTHROUGH);
-        case K_ETC2A: return cvttmi_encode_etc2_alpha(ctx, out, in, n, o);
-        case K_A11U: return cvttmi_encode_etc2_alpha11(ctx, out, reinterpret_cast<const int16_t *>(in), n, 0, o);
-        case K_A11S: return cvttmi_encode_etc2_alpha11(ctx, out, reinterpret_cast<const int16_t *>(in), n, 1, o);
-        }
-        return CVTTMI_E_INVALID;
+        return cvttmi_encode(ctx, k.kind, out, in, n, &k.options, k.hasPlan ? &k.plan : NULL, k.hasAlloc ? &k.allocOptions : NULL);
     }
 
     // the device side of a coalescer slot
@@ -169,11 +146,15 @@ namespace
         return on;
     }
 
-    // one reference-style call: a group of 8 blocks, `inBytes` in, `outBytes` out
-    void oneGroup(int kind, uint8_t *pBC, const void *pBlocks, size_t inBytes, size_t outBytes, const cvtt::Options &options, const char *what,
+    // one reference-style call: a group of 8 blocks of `format`
+    void oneGroup(int format, uint8_t *pBC, const void *pBlocks, const cvtt::Options &options, const char *what,
                   const cvttmi_options *alloc = NULL, const cvtt::BC7EncodingPlan *plan = NULL)
     {
-        const CallKey key = makeKey(kind, options, alloc, plan);
+        size_t outBytes = 0, inBytes = 0;
+        cvttmi_format_info(format, &outBytes, &inBytes, NULL);
+        inBytes *= cvtt::NumParallelBlocks;
+        outBytes *= cvtt::NumParallelBlocks;
+        const CallKey key = makeKey(format, options, alloc, plan);
         if (coalesceEnabled())
         {
             void *ran = NULL;
@@ -248,6 +229,19 @@ namespace
     {
         void *context;
     };
+
+    // one *Batch call: any multiple of 8 blocks of `format`.  shard: the call is one of those that go over the device list
+    // when that has several entries and the call is large enough (cvtt_mi355x.h, cvttmi_dropin_set_devices).
+    void batch(int format, uint8_t *pBC, const void *pBlocks, size_t numBlocks, const cvtt::Options &options, const char *what, bool shard = false,
+               const cvttmi_options *alloc = NULL, const cvtt::BC7EncodingPlan *plan = NULL)
+    {
+        const uint8_t *in = static_cast<const uint8_t *>(pBlocks);
+        const cvttmi_bc7_plan *p = reinterpret_cast<const cvttmi_bc7_plan *>(plan);
+        if (shard)
+            if (cvttmi_multi *m = multiFor(numBlocks))
+                return checkMulti(m, cvttmi_multi_encode(m, format, pBC, in, numBlocks, 0, opt(options), p), what);
+        check(cvttmi_encode(context(), format, pBC, in, numBlocks, opt(options), p, alloc), what);
+    }
 }
 
 cvtt::Options::Options()
@@ -280,93 +274,27 @@ namespace cvtt
             return true; // like the reference (BC67.cpp:3482)
         }
 
-        void EncodeBC7Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, const BC7EncodingPlan &plan)
-        {
-            if (cvttmi_multi *m = multiFor(numBlocks))
-                return checkMulti(m, cvttmi_multi_encode(m, CVTTMI_FMT_BC7, pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, 0, opt(options),
-                                                         reinterpret_cast<const cvttmi_bc7_plan *>(&plan)), "EncodeBC7");
-            check(cvttmi_encode_bc7(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options),
-                                    reinterpret_cast<const cvttmi_bc7_plan *>(&plan)), "EncodeBC7");
-        }
-        void EncodeBC1Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options)
-        {
-            if (cvttmi_multi *m = multiFor(numBlocks))
-                return checkMulti(m, cvttmi_multi_encode(m, CVTTMI_FMT_BC1, pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, 0, opt(options), NULL), "EncodeBC1");
-            check(cvttmi_encode_bc1(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options)), "EncodeBC1");
-        }
-#define CVTT_S3TC_BATCH(NAME, PIXELTYPE, CALL)                                                                                  \
-        void NAME##Batch(uint8_t *pBC, const PIXELTYPE *pBlocks, size_t numBlocks, const Options &options)                      \
-        {                                                                                                                       \
-            check(CALL, #NAME);                                                                                                 \
-        }                                                                                                                       \
-        void NAME(uint8_t *pBC, const PIXELTYPE *pBlocks, const Options &options) { oneGroup(K_##NAME, pBC, pBlocks, sizeof(PIXELTYPE) * NumParallelBlocks, OUTBYTES * NumParallelBlocks, options, #NAME); }
-#define K_EncodeBC2 K_BC2
-#define K_EncodeBC3 K_BC3
-#define K_EncodeBC4U K_BC4U
-#define K_EncodeBC4S K_BC4S
-#define K_EncodeBC5U K_BC5U
-#define K_EncodeBC5S K_BC5S
-#define OUTBYTES 16
-        CVTT_S3TC_BATCH(EncodeBC2, PixelBlockU8, cvttmi_encode_bc2(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options)))
-        CVTT_S3TC_BATCH(EncodeBC3, PixelBlockU8, cvttmi_encode_bc3(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options)))
-#undef OUTBYTES
-#define OUTBYTES 8
-        CVTT_S3TC_BATCH(EncodeBC4U, PixelBlockU8, cvttmi_encode_bc4(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 0))
-        CVTT_S3TC_BATCH(EncodeBC4S, PixelBlockS8, cvttmi_encode_bc4(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 1))
-#undef OUTBYTES
-#define OUTBYTES 16
-        CVTT_S3TC_BATCH(EncodeBC5U, PixelBlockU8, cvttmi_encode_bc5(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 0))
-        CVTT_S3TC_BATCH(EncodeBC5S, PixelBlockS8, cvttmi_encode_bc5(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 1))
-#undef CVTT_S3TC_BATCH
-#undef OUTBYTES
-
-        void EncodeBC6HUBatch(uint8_t *pBC, const PixelBlockF16 *pBlocks, size_t numBlocks, const Options &options)
-        {
-            if (cvttmi_multi *m = multiFor(numBlocks))
-                return checkMulti(m, cvttmi_multi_encode(m, CVTTMI_FMT_BC6HU, pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, 0, opt(options), NULL), "EncodeBC6HU");
-            check(cvttmi_encode_bc6h(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 0), "EncodeBC6HU");
-        }
-        void EncodeBC6HSBatch(uint8_t *pBC, const PixelBlockF16 *pBlocks, size_t numBlocks, const Options &options)
-        {
-            if (cvttmi_multi *m = multiFor(numBlocks))
-                return checkMulti(m, cvttmi_multi_encode(m, CVTTMI_FMT_BC6HS, pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, 0, opt(options), NULL), "EncodeBC6HS");
-            check(cvttmi_encode_bc6h(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), 1), "EncodeBC6HS");
-        }
-        void EncodeETC2PunchthroughAlphaBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, ETC2CompressionData *data)
-        {
-            check(cvttmi_encode_etc2_with_data(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), allocOpt(data), CVTTMI_ETC2_PUNCHTHROUGH),
-                  "EncodeETC2PunchthroughAlpha");
-        }
-        void EncodeETC1Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options)
-        {
-            check(cvttmi_encode_etc1(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options)), "EncodeETC1");
-        }
-        void EncodeETC2Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, ETC2CompressionData *data)
-        {
-            check(cvttmi_encode_etc2_with_data(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), allocOpt(data), CVTTMI_ETC2_RGB), "EncodeETC2");
-        }
+        void EncodeBC7Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, const BC7EncodingPlan &plan) { batch(CVTTMI_FMT_BC7, pBC, pBlocks, numBlocks, options, "EncodeBC7", true, NULL, &plan); }
+        void EncodeBC1Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC1, pBC, pBlocks, numBlocks, options, "EncodeBC1", true); }
+        void EncodeBC2Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC2, pBC, pBlocks, numBlocks, options, "EncodeBC2"); }
+        void EncodeBC3Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC3, pBC, pBlocks, numBlocks, options, "EncodeBC3"); }
+        void EncodeBC4UBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC4U, pBC, pBlocks, numBlocks, options, "EncodeBC4U"); }
+        void EncodeBC4SBatch(uint8_t *pBC, const PixelBlockS8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC4S, pBC, pBlocks, numBlocks, options, "EncodeBC4S"); }
+        void EncodeBC5UBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC5U, pBC, pBlocks, numBlocks, options, "EncodeBC5U"); }
+        void EncodeBC5SBatch(uint8_t *pBC, const PixelBlockS8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC5S, pBC, pBlocks, numBlocks, options, "EncodeBC5S"); }
+        void EncodeBC6HUBatch(uint8_t *pBC, const PixelBlockF16 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC6HU, pBC, pBlocks, numBlocks, options, "EncodeBC6HU", true); }
+        void EncodeBC6HSBatch(uint8_t *pBC, const PixelBlockF16 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_BC6HS, pBC, pBlocks, numBlocks, options, "EncodeBC6HS", true); }
+        void EncodeETC1Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_ETC1, pBC, pBlocks, numBlocks, options, "EncodeETC1"); }
+        void EncodeETC2Batch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, ETC2CompressionData *data) { batch(CVTTMI_FMT_ETC2_RGB, pBC, pBlocks, numBlocks, options, "EncodeETC2", false, allocOpt(data)); }
         void EncodeETC2RGBABatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, ETC2CompressionData *data)
         {
             // (sharded only when the scratch was allocated with the Options of this call: the sharded form has one Options argument)
-            if (!allocOpt(data) || memcmp(allocOpt(data), &options, sizeof(cvttmi_options)) == 0)
-                if (cvttmi_multi *m = multiFor(numBlocks))
-                    return checkMulti(m, cvttmi_multi_encode(m, CVTTMI_FMT_ETC2_RGBA, pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, 0, opt(options), NULL), "EncodeETC2RGBA");
-            check(cvttmi_encode_etc2_with_data(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options), allocOpt(data), CVTTMI_ETC2_RGBA), "EncodeETC2RGBA");
+            const bool sameOptions = !allocOpt(data) || memcmp(allocOpt(data), &options, sizeof(cvttmi_options)) == 0;
+            batch(CVTTMI_FMT_ETC2_RGBA, pBC, pBlocks, numBlocks, options, "EncodeETC2RGBA", sameOptions, allocOpt(data));
         }
-        void EncodeETC2AlphaBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options)
-        {
-            check(cvttmi_encode_etc2_alpha(context(), pBC, reinterpret_cast<const uint8_t *>(pBlocks), numBlocks, opt(options)), "EncodeETC2Alpha");
-        }
-
-        void EncodeETC2Alpha11Batch(uint8_t *pBC, const PixelBlockScalarS16 *pBlocks, size_t numBlocks, bool isSigned, const Options &options)
-        {
-            check(cvttmi_encode_etc2_alpha11(context(), pBC, reinterpret_cast<const int16_t *>(pBlocks), numBlocks, isSigned ? 1 : 0, opt(options)),
-                  "EncodeETC2Alpha11");
-        }
-        void EncodeETC2Alpha11(uint8_t *pBC, const PixelBlockScalarS16 *pBlocks, bool isSigned, const Options &options)
-        {
-            oneGroup(isSigned ? K_A11S : K_A11U, pBC, pBlocks, sizeof(PixelBlockScalarS16) * NumParallelBlocks, 8 * NumParallelBlocks, options, "EncodeETC2Alpha11");
-        }
+        void EncodeETC2PunchthroughAlphaBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options, ETC2CompressionData *data) { batch(CVTTMI_FMT_ETC2_PUNCHTHROUGH, pBC, pBlocks, numBlocks, options, "EncodeETC2PunchthroughAlpha", false, allocOpt(data)); }
+        void EncodeETC2AlphaBatch(uint8_t *pBC, const PixelBlockU8 *pBlocks, size_t numBlocks, const Options &options) { batch(CVTTMI_FMT_EAC_ALPHA, pBC, pBlocks, numBlocks, options, "EncodeETC2Alpha"); }
+        void EncodeETC2Alpha11Batch(uint8_t *pBC, const PixelBlockScalarS16 *pBlocks, size_t numBlocks, bool isSigned, const Options &options) { batch(isSigned ? CVTTMI_FMT_R11S : CVTTMI_FMT_R11U, pBC, pBlocks, numBlocks, options, "EncodeETC2Alpha11"); }
         void DecodeBC7Batch(PixelBlockU8 *pBlocks, const uint8_t *pBC, size_t numBlocks)
         {
             check(cvttmi_decode_bc7(context(), reinterpret_cast<uint8_t *>(pBlocks), pBC, numBlocks), "DecodeBC7");
@@ -384,15 +312,22 @@ namespace cvtt
         void DecodeBC6HS(PixelBlockF16 *pBlocks, const uint8_t *pBC) { DecodeBC6HSBatch(pBlocks, pBC, NumParallelBlocks); }
 
         // The reference's own entry points: one group of NumParallelBlocks blocks per call (coalesced across caller threads)
-        void EncodeBC7(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, const BC7EncodingPlan &plan) { oneGroup(K_BC7, pBC, pBlocks, 512, 128, options, "EncodeBC7", NULL, &plan); }
-        void EncodeBC1(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(K_BC1, pBC, pBlocks, 512, 64, options, "EncodeBC1"); }
-        void EncodeBC6HU(uint8_t *pBC, const PixelBlockF16 *pBlocks, const Options &options) { oneGroup(K_BC6HU, pBC, pBlocks, 1024, 128, options, "EncodeBC6HU"); }
-        void EncodeBC6HS(uint8_t *pBC, const PixelBlockF16 *pBlocks, const Options &options) { oneGroup(K_BC6HS, pBC, pBlocks, 1024, 128, options, "EncodeBC6HS"); }
-        void EncodeETC2PunchthroughAlpha(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(K_ETC2PT, pBC, pBlocks, 512, 64, options, "EncodeETC2PunchthroughAlpha", allocOpt(data)); }
-        void EncodeETC1(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC1CompressionData *) { oneGroup(K_ETC1, pBC, pBlocks, 512, 64, options, "EncodeETC1"); }
-        void EncodeETC2(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(K_ETC2, pBC, pBlocks, 512, 64, options, "EncodeETC2", allocOpt(data)); }
-        void EncodeETC2RGBA(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(K_ETC2RGBA, pBC, pBlocks, 512, 128, options, "EncodeETC2RGBA", allocOpt(data)); }
-        void EncodeETC2Alpha(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(K_ETC2A, pBC, pBlocks, 512, 64, options, "EncodeETC2Alpha"); }
+        void EncodeBC7(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, const BC7EncodingPlan &plan) { oneGroup(CVTTMI_FMT_BC7, pBC, pBlocks, options, "EncodeBC7", NULL, &plan); }
+        void EncodeBC1(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC1, pBC, pBlocks, options, "EncodeBC1"); }
+        void EncodeBC2(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC2, pBC, pBlocks, options, "EncodeBC2"); }
+        void EncodeBC3(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC3, pBC, pBlocks, options, "EncodeBC3"); }
+        void EncodeBC4U(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC4U, pBC, pBlocks, options, "EncodeBC4U"); }
+        void EncodeBC4S(uint8_t *pBC, const PixelBlockS8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC4S, pBC, pBlocks, options, "EncodeBC4S"); }
+        void EncodeBC5U(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC5U, pBC, pBlocks, options, "EncodeBC5U"); }
+        void EncodeBC5S(uint8_t *pBC, const PixelBlockS8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC5S, pBC, pBlocks, options, "EncodeBC5S"); }
+        void EncodeBC6HU(uint8_t *pBC, const PixelBlockF16 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC6HU, pBC, pBlocks, options, "EncodeBC6HU"); }
+        void EncodeBC6HS(uint8_t *pBC, const PixelBlockF16 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_BC6HS, pBC, pBlocks, options, "EncodeBC6HS"); }
+        void EncodeETC2PunchthroughAlpha(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(CVTTMI_FMT_ETC2_PUNCHTHROUGH, pBC, pBlocks, options, "EncodeETC2PunchthroughAlpha", allocOpt(data)); }
+        void EncodeETC1(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC1CompressionData *) { oneGroup(CVTTMI_FMT_ETC1, pBC, pBlocks, options, "EncodeETC1"); }
+        void EncodeETC2(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(CVTTMI_FMT_ETC2_RGB, pBC, pBlocks, options, "EncodeETC2", allocOpt(data)); }
+        void EncodeETC2RGBA(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options, ETC2CompressionData *data) { oneGroup(CVTTMI_FMT_ETC2_RGBA, pBC, pBlocks, options, "EncodeETC2RGBA", allocOpt(data)); }
+        void EncodeETC2Alpha(uint8_t *pBC, const PixelBlockU8 *pBlocks, const Options &options) { oneGroup(CVTTMI_FMT_EAC_ALPHA, pBC, pBlocks, options, "EncodeETC2Alpha"); }
+        void EncodeETC2Alpha11(uint8_t *pBC, const PixelBlockScalarS16 *pBlocks, bool isSigned, const Options &options) { oneGroup(isSigned ? CVTTMI_FMT_R11S : CVTTMI_FMT_R11U, pBC, pBlocks, options, "EncodeETC2Alpha11"); }
 
         // The reference places 136 KB of scratch in caller memory (ETC.cpp:3100-3115); here the allocator context survives
         // so that ReleaseETC2Data can hand the block back, and the Options, whose colour weights fix the chroma axes.

@@ -191,50 +191,6 @@ namespace
 {
     struct ErrText { char t[160]; };
 
-    bool formatSizes(int format, size_t &inBpb, size_t &outBpb)
-    {
-        inBpb = 64;
-        outBpb = 16;
-        switch (format)
-        {
-        case CVTTMI_FMT_BC7: return true;
-        case CVTTMI_FMT_BC1: outBpb = 8; return true;
-        case CVTTMI_FMT_BC6HU: case CVTTMI_FMT_BC6HS: inBpb = 128; return true;
-        case CVTTMI_FMT_ETC2_RGB: outBpb = 8; return true;
-        case CVTTMI_FMT_ETC2_RGBA: return true;
-        }
-        return false;
-    }
-
-    // one shard, host buffers: the host-pointer entry point of its context (pinned staging, PCIe pipelined with the search)
-    int encodeHostShard(cvttmi_context *c, int format, uint8_t *o, const uint8_t *b, size_t n, const cvttmi_options *options, const cvttmi_bc7_plan *plan)
-    {
-        switch (format)
-        {
-        case CVTTMI_FMT_BC7: return cvttmi_encode_bc7(c, o, b, n, options, plan);
-        case CVTTMI_FMT_BC1: return cvttmi_encode_bc1(c, o, b, n, options);
-        case CVTTMI_FMT_BC6HU: return cvttmi_encode_bc6h(c, o, b, n, options, 0);
-        case CVTTMI_FMT_BC6HS: return cvttmi_encode_bc6h(c, o, b, n, options, 1);
-        case CVTTMI_FMT_ETC2_RGB: return cvttmi_encode_etc2(c, o, b, n, options);
-        case CVTTMI_FMT_ETC2_RGBA: return cvttmi_encode_etc2_rgba(c, o, b, n, options);
-        }
-        return CVTTMI_E_INVALID;
-    }
-
-    int encodeDeviceShard(cvttmi_context *c, int format, void *o, const void *b, size_t n, const cvttmi_options *options, const cvttmi_bc7_plan *plan, hipStream_t st)
-    {
-        switch (format)
-        {
-        case CVTTMI_FMT_BC7: return cvttmi_encode_bc7_device(c, o, b, n, options, plan, st);
-        case CVTTMI_FMT_BC1: return cvttmi_encode_bc1_device(c, o, b, n, options, st);
-        case CVTTMI_FMT_BC6HU: return cvttmi_encode_bc6h_device(c, o, b, n, options, 0, st);
-        case CVTTMI_FMT_BC6HS: return cvttmi_encode_bc6h_device(c, o, b, n, options, 1, st);
-        case CVTTMI_FMT_ETC2_RGB: return cvttmi_encode_etc2_device(c, o, b, n, options, st);
-        case CVTTMI_FMT_ETC2_RGBA: return cvttmi_encode_etc2_rgba_device(c, o, b, n, options, st);
-        }
-        return CVTTMI_E_INVALID;
-    }
-
     // Shard r of a device-resident job: search on devices[r] (launch on the shard's own stream), then -- unless the shard runs on
     // the root device and wrote its slice of the root buffer directly -- one peer copy of the packed blocks to the root buffer.
     // `err` receives the failing HIP call's text (a fixed buffer: this runs on a worker thread and must not throw).
@@ -275,7 +231,7 @@ namespace
                 (void)hipGetLastError();
             }
         }
-        const int rc = encodeDeviceShard(m->ctx[r], format, target, d_in, n, options, plan, st);
+        const int rc = cvttmi_encode_device(m->ctx[r], format, target, d_in, n, options, plan, NULL, st);
         if (rc != CVTTMI_OK) { snprintf(err, sizeof(err), "%s", cvttmi_last_error(m->ctx[r])); return rc; }
         if (!direct)
         {
@@ -298,8 +254,8 @@ namespace
             return CVTTMI_E_INVALID;
         }
         std::lock_guard<std::mutex> lock(m->mu);
-        size_t inBpb = 64, outBpb = 16;
-        if (!formatSizes(format, inBpb, outBpb)) { noteError(m, "unknown format"); return CVTTMI_E_INVALID; }
+        size_t inBpb = 0, outBpb = 0;
+        if (cvttmi_format_info(format, &outBpb, &inBpb, NULL) != CVTTMI_OK) { noteError(m, "unknown format"); return CVTTMI_E_INVALID; }
         if (format == CVTTMI_FMT_BC7 && !plan) { noteError(m, "BC7 needs a plan"); return CVTTMI_E_INVALID; }
         if (!out || (!blocks && !d_shards) || !options || (numBlocks % 8) != 0)
         {
@@ -336,7 +292,8 @@ namespace
                     if (d_shards)
                         rcs[r] = deviceShard(m, r, format, out + lo * outBpb, d_shards[r], hi - lo, outBpb, options, plan, errs[r].t);
                     else
-                        rcs[r] = encodeHostShard(m->ctx[r], format, out + lo * outBpb, blocks + lo * inBpb, hi - lo, options, plan);
+                        // the host-pointer entry point of the shard's context (pinned staging, PCIe pipelined with the search)
+                        rcs[r] = cvttmi_encode(m->ctx[r], format, out + lo * outBpb, blocks + lo * inBpb, hi - lo, options, plan, NULL);
                 }));
             }
             catch (...) // no thread to be had: finish what was started, then report

@@ -142,6 +142,30 @@ int cvttmi_host_free(cvttmi_context *ctx, void *ptr);
 int cvttmi_host_register(cvttmi_context *ctx, void *ptr, size_t bytes);
 int cvttmi_host_unregister(cvttmi_context *ctx, void *ptr);
 
+/* Texture formats: the one id a format has from here to the kernel launchers -- the generic encode, decode, measure and
+ * multi-device entries all take it.  cvttmi_format_info: bytes per packed block, bytes per input / decoded block (PixelBlockU8
+ * 64, PixelBlockF16 128, PixelBlockScalarS16 32) and the channels the format stores (bit c = channel c), from the library's
+ * one table; needs no context; CVTTMI_E_INVALID for an unknown id; any out pointer may be NULL. */
+#define CVTTMI_FMT_BC7 0
+#define CVTTMI_FMT_BC1 1
+#define CVTTMI_FMT_BC6HU 2
+#define CVTTMI_FMT_BC6HS 3
+#define CVTTMI_FMT_ETC2_RGB 4
+#define CVTTMI_FMT_ETC2_RGBA 5
+#define CVTTMI_FMT_BC2 6
+#define CVTTMI_FMT_BC3 7
+#define CVTTMI_FMT_BC4U 8
+#define CVTTMI_FMT_BC4S 9
+#define CVTTMI_FMT_BC5U 10
+#define CVTTMI_FMT_BC5S 11
+#define CVTTMI_FMT_ETC1 12
+#define CVTTMI_FMT_ETC2_PUNCHTHROUGH 13
+#define CVTTMI_FMT_EAC_ALPHA 14
+#define CVTTMI_FMT_R11U 15
+#define CVTTMI_FMT_R11S 16
+#define CVTTMI_FMT_COUNT 17
+int cvttmi_format_info(int format, size_t *packedBytes, size_t *blockBytes, uint32_t *channelMask);
+
 /* ---- device-resident entry points: d_blocks / d_out are HBM pointers on the context's
  * device; the launch is asynchronous on `hipStream` (a hipStream_t, NULL = default).
  * Streams: a context owns ONE set of device work space (BC7 hand-over list, punch-through trial table and plan ring; up to 256 MB
@@ -168,6 +192,17 @@ int cvttmi_host_unregister(cvttmi_context *ctx, void *ptr);
  * device pointer that breaks the rule is rejected with CVTTMI_E_INVALID before anything is queued; nothing is written.
  * HOST pointers (the entry points without _device) need no alignment at all, like the reference's byte arrays: pageable and
  * misaligned page-locked buffers are staged, block-aligned page-locked ones are transferred in place. ---- */
+
+/* Every encoder by format id: the entry points named after the reference's calls, below, are this call with their id, and
+ * describe what each format reads, writes and uses of `options`.  format = CVTTMI_FMT_*; an unknown id is CVTTMI_E_INVALID.
+ * plan: required for BC7 (NULL: CVTTMI_E_INVALID, nothing is launched), ignored by every other format.  allocOptions: read only
+ * by ETC2 RGB / RGBA / punch-through -- the Options AllocETC2Data was given, see cvttmi_encode_etc2_with_data; NULL = `options`
+ * -- and ignored elsewhere.  cvttmi_encode is the host-buffer form (see "host-buffer convenience entry points"). */
+int cvttmi_encode_device(cvttmi_context *ctx, int format, void *d_out, const void *d_blocks, size_t numBlocks,
+                         const cvttmi_options *options, const cvttmi_bc7_plan *plan,
+                         const cvttmi_options *allocOptions, void *hipStream);
+int cvttmi_encode(cvttmi_context *ctx, int format, void *out, const void *blocks, size_t numBlocks,
+                  const cvttmi_options *options, const cvttmi_bc7_plan *plan, const cvttmi_options *allocOptions);
 
 /* replaces cvtt::Kernels::EncodeBC7 (ConvectionKernels_API.cpp:41-54): numBlocks * 64 B
  * of PixelBlockU8 in, numBlocks * 16 B out. */
@@ -231,7 +266,9 @@ int cvttmi_encode_etc2_punchthrough_alpha(cvttmi_context *ctx, uint8_t *out, con
  * computes them from the Options given to AllocETC2Data (ConvectionKernels_ETC.cpp:3117-3145) -- while the error weights
  * come from the Options of each Encode call.  `allocOptions` = the Options the caller passed to AllocETC2Data (only its
  * red / green / blue weights are read; NULL = `options`).  kind: CVTTMI_ETC2_RGB = EncodeETC2, CVTTMI_ETC2_RGBA =
- * EncodeETC2RGBA, CVTTMI_ETC2_PUNCHTHROUGH = EncodeETC2PunchthroughAlpha (the three calls that take the scratch). */
+ * EncodeETC2RGBA, CVTTMI_ETC2_PUNCHTHROUGH = EncodeETC2PunchthroughAlpha (the three calls that take the scratch).  The three
+ * values are aliases of what this entry has always taken, kept for its callers; it maps them to CVTTMI_FMT_ETC2_RGB / _RGBA /
+ * _PUNCHTHROUGH and is cvttmi_encode[_device] with that id.  Any other kind is CVTTMI_E_INVALID. */
 #define CVTTMI_ETC2_RGB 0
 #define CVTTMI_ETC2_RGBA 1
 #define CVTTMI_ETC2_PUNCHTHROUGH 4
@@ -315,7 +352,7 @@ int cvttmi_decode_bc6h_device(cvttmi_context *ctx, void *d_blocksF16, const void
 int cvttmi_decode_bc6h(cvttmi_context *ctx, uint8_t *blocksF16, const uint8_t *bc, size_t numBlocks, int isSigned);
 
 /* ---- every format: decode, and the encoding error in one pass (not part of the reference's API) ----
- * format = CVTTMI_FMT_* below.  A decoder writes the layout its encoder reads:
+ * format = CVTTMI_FMT_* (above).  A decoder writes the layout its encoder reads:
  *   BC7, BC1, BC2, BC3, ETC1, ETC2 RGB / RGBA / punch-through, EAC alpha: PixelBlockU8 (64 B; BC1 three-colour index 3 and
  *     punch-through transparent texels = (0,0,0,0); ETC RGB alpha = 255; EAC alpha = (0,0,0,a))
  *   BC4U / BC5U: PixelBlockU8 (r,0,0,255) / (r,g,0,255);  BC4S / BC5S: PixelBlockS8 (r,0,0,127) / (r,g,0,127)
@@ -333,18 +370,6 @@ int cvttmi_decode_bc6h(cvttmi_context *ctx, uint8_t *blocksF16, const uint8_t *b
  * (host entries: chunks of 2^17) add into the totals in order.  No float atomics: the same input gives bit-identical totals
  * on every run and stream.  The partials live in one slab per context: like the BC7 hand-over list, a call on another
  * stream than the previous one waits for it (one context per stream to overlap work). ---- */
-#define CVTTMI_FMT_BC2 6
-#define CVTTMI_FMT_BC3 7
-#define CVTTMI_FMT_BC4U 8
-#define CVTTMI_FMT_BC4S 9
-#define CVTTMI_FMT_BC5U 10
-#define CVTTMI_FMT_BC5S 11
-#define CVTTMI_FMT_ETC1 12
-#define CVTTMI_FMT_ETC2_PUNCHTHROUGH 13
-#define CVTTMI_FMT_EAC_ALPHA 14
-#define CVTTMI_FMT_R11U 15
-#define CVTTMI_FMT_R11S 16
-#define CVTTMI_FMT_COUNT 17
 typedef struct cvttmi_error_totals
 {
     uint64_t sse[4];      /* integer formats: exact per-channel sums; 0 for channels the format does not store */
@@ -390,12 +415,6 @@ double cvttmi_psnr(const cvttmi_error_totals *t, uint32_t channelMask);
  * No call of this section lets a C++ exception out; allocation failures come back as CVTTMI_E_HIP.
  * Between processes (one per GPU) the packed output is gathered with RCCL send/recv over xGMI instead: sharding.py,
  * bench.py --gpus N. ---- */
-#define CVTTMI_FMT_BC7 0
-#define CVTTMI_FMT_BC1 1
-#define CVTTMI_FMT_BC6HU 2
-#define CVTTMI_FMT_BC6HS 3
-#define CVTTMI_FMT_ETC2_RGB 4
-#define CVTTMI_FMT_ETC2_RGBA 5
 typedef struct cvttmi_multi cvttmi_multi;
 int cvttmi_shard_block_rows(size_t blockRows, size_t blocksPerRow, int rank, int world, size_t *firstBlock, size_t *lastBlock);
 int cvttmi_multi_create(cvttmi_multi **out, const int *devices, int numDevices);
@@ -406,7 +425,10 @@ cvttmi_context *cvttmi_multi_context(cvttmi_multi *m, int index);
 int cvttmi_multi_last_shard(const cvttmi_multi *m, int index, size_t *firstBlock, size_t *lastBlock);
 int cvttmi_multi_set_rcp_table(cvttmi_multi *m, const float lut[17]);
 int cvttmi_multi_set_exhaustive(cvttmi_multi *m, int exhaustive);
-/* format = CVTTMI_FMT_*; plan: BC7 only (NULL otherwise); host buffers (page-locked ones are transferred in place) */
+/* format = CVTTMI_FMT_*: every format of the table (cvttmi_format_info gives the sizes; each shard is one cvttmi_encode /
+ * cvttmi_encode_device call on its context, so what those accept is accepted here -- all seventeen ids, where this section
+ * took six before).  plan: BC7 only (NULL otherwise); the ETC2 formats take the chroma axes from `options`.  Host buffers
+ * (page-locked ones are transferred in place). */
 int cvttmi_multi_encode(cvttmi_multi *m, int format, uint8_t *out, const uint8_t *blocks, size_t numBlocks, size_t blocksPerRow,
                         const cvttmi_options *options, const cvttmi_bc7_plan *plan);
 /* Device-resident callers (the tiling kernel or an upload of the caller's own has put every shard where it is searched):

@@ -348,3 +348,34 @@ def test_numpy_only_process_then_torch_share_one_runtime():
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     assert p.stdout.split()[-1] == "1"
+
+
+def test_format_info_is_the_one_table_behind_every_python_table():
+    """cvttmi_format_info (the library's one row per CVTTMI_FMT_* id) against the tables Python keeps: api.TEXTURE_FORMATS for
+    every name of an id, MultiContext.FORMATS, and the bytes per block container.FORMATS writes.  No context, no device."""
+    from convectionkernels_amd import api, container
+    lib = api.load_library()
+    E_INVALID = -1
+
+    def info(fid):
+        packed, block, mask = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint32()
+        rc = lib.cvttmi_format_info(fid, ctypes.byref(packed), ctypes.byref(block), ctypes.byref(mask))
+        return rc, (packed.value, block.value, mask.value)
+
+    for fid in range(17):
+        rc, row = info(fid)
+        assert rc == 0, fid
+        names = [n for n, r in api.TEXTURE_FORMATS.items() if r[0] == fid]
+        assert names, "id %d has no name" % fid
+        for name in names:
+            assert api.TEXTURE_FORMATS[name] == (fid,) + row, name
+            assert api.MultiContext.FORMATS[name] == (fid, row[1], row[0]), name
+            if name in container.FORMATS:
+                assert container.FORMATS[name][0] == row[0], name
+        assert lib.cvttmi_format_info(fid, None, None, None) == 0  # any out pointer may be NULL
+    assert set(api.MultiContext.FORMATS) == set(api.TEXTURE_FORMATS)
+    assert set(container.FORMATS) <= set(api.TEXTURE_FORMATS)
+    assert sorted({r[0] for r in api.TEXTURE_FORMATS.values()}) == list(range(17))
+    for fid in (-1, 17):
+        rc, row = info(fid)
+        assert rc == E_INVALID and row == (0, 0, 0), fid  # nothing is written for an unknown id

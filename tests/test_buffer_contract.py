@@ -767,3 +767,132 @@ def test_misaligned_device_pointers_are_rejected_by_the_other_entries(ctx):
         for d in _forbidden(bpb):
             _rejected(lib, h, lib.cvttmi_compact_rows_device(h, out.data_ptr() + d, packed.data_ptr(), 8, 4, bpb, None), [check], "compact output +%d" % d)
             _rejected(lib, h, lib.cvttmi_compact_rows_device(h, out.data_ptr(), packed.data_ptr() + d, 8, 4, bpb, None), [check], "compact input +%d" % d)
+
+
+# ---------------------------------------------------------------- the generic entries: one call, a format id
+
+# ENCODERS name -> (CVTTMI_FMT_* id, the Options AllocETC2Data was given or None): the same encode through cvttmi_encode[_device]
+GENERIC = {name: (api.TEXTURE_FORMATS["eac" if name == "etc2alpha" else name][0], None) for name in ENCODERS if not name.startswith("with_data")}
+GENERIC.update(with_data_rgb=(4, _ALLOC_OPT), with_data_rgba=(5, _ALLOC_OPT), with_data_punchthrough=(13, _ALLOC_OPT))
+assert sorted({fid for fid, _ in GENERIC.values()}) == list(range(17))
+# 8: one group, a part-filled wave in every mapping; 264 = 16 * 16 + 8 = 4 * 64 + 8: ends inside a wave of the 16-blocks-per-wave
+# mappings (BC7, BC6H) and inside a workgroup of the 64- and 256-lane ones
+GENERIC_SIZES = (8, 264)
+
+
+def _generic_args(name, opt):
+    """(format id, options, plan, allocOptions) as cvttmi_encode[_device] takes them: the plan for BC7 alone"""
+    fid, alloc = GENERIC[name]
+    return fid, _addr(opt), (_addr(_PLAN) if name == "bc7" else None), (_addr(alloc) if alloc is not None else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(GENERIC))
+def test_generic_device_entry_equals_the_named_one(ctx, name):
+    """cvttmi_encode_device(format id) writes the bytes of the format's named *_device entry (held to the oracle above), all of
+    them and none outside, with input and output 1 and 3 blocks into their allocations"""
+    lib, h = ctx._lib, ctx._h
+    kind, in_bpb, out_bpb, named, _, _ = ENCODERS[name]
+    blocks, opt = source_blocks(kind), api.Options()
+    fid, optp, planp, allocp = _generic_args(name, opt)
+    for n in GENERIC_SIZES:
+        for in_off, out_off in ((1, 3), (3, 1)):
+            what = "generic %s (format %d), %d blocks, input +%d, output +%d blocks" % (name, fid, n, in_off, out_off)
+            src, unchanged = guarded.device_input(blocks[:n], in_off * in_bpb, what=what + ": input")
+            ref, ref_check = guarded.device_buffer(n * out_bpb, out_off * out_bpb, 0x5A, what=what + ": named entry")
+            assert named(lib, h, ref.data_ptr(), src.data_ptr(), n, opt) == 0, (what, lib.cvttmi_last_error(h))
+            exp = ref_check.payload()
+            ref_check.no_poison_blocks(8)
+            out, check = guarded.device_buffer(n * out_bpb, out_off * out_bpb, 0xA5, what=what)
+            assert lib.cvttmi_encode_device(h, fid, out.data_ptr(), src.data_ptr(), n, optp, planp, allocp, None) == 0, (what, lib.cvttmi_last_error(h))
+            check(exp)
+            check.no_poison_blocks(8)
+            unchanged()
+
+
+GENERIC_HOST = {
+    "bc7": lambda lib, h, o, i, n, opt: lib.cvttmi_encode_bc7(h, o, i, n, _addr(opt), _addr(_PLAN)),
+    "bc4s": lambda lib, h, o, i, n, opt: lib.cvttmi_encode_bc4(h, o, i, n, _addr(opt), 1),
+    "bc6hs": lambda lib, h, o, i, n, opt: lib.cvttmi_encode_bc6h(h, o, i, n, _addr(opt), 1),
+    "etc2rgba": lambda lib, h, o, i, n, opt: lib.cvttmi_encode_etc2_rgba(h, o, i, n, _addr(opt)),
+    "r11s": lambda lib, h, o, i, n, opt: lib.cvttmi_encode_etc2_alpha11(h, o, i, n, 1, _addr(opt)),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(GENERIC_HOST))
+def test_generic_host_entry_equals_the_named_one(ctx, name):
+    """cvttmi_encode on host pointers one byte into their allocations, 264 blocks, against the named host entry"""
+    lib, h = ctx._lib, ctx._h
+    kind, in_bpb, out_bpb = ENCODERS[name][:3]
+    opt, n = api.Options(), 264
+    fid, optp, planp, allocp = _generic_args(name, opt)
+    what = "generic host %s (format %d), %d blocks, input and output +1 byte" % (name, fid, n)
+    src, unchanged = _host_in(source_blocks(kind)[:n], 1)
+    ref, ref_check = guarded.host_buffer(n * out_bpb, 1, 0x5A, what=what + ": named entry")
+    assert GENERIC_HOST[name](lib, h, ref.ctypes.data, src.ctypes.data, n, opt) == 0, (what, lib.cvttmi_last_error(h))
+    exp = ref_check.payload()
+    ref_check.no_poison_blocks(8)
+    out, check = guarded.host_buffer(n * out_bpb, 1, 0xA5, what=what)
+    assert lib.cvttmi_encode(h, fid, out.ctypes.data, src.ctypes.data, n, optp, planp, allocp) == 0, (what, lib.cvttmi_last_error(h))
+    check(exp)
+    check.no_poison_blocks(8)
+    unchanged()
+
+
+@pytest.mark.gpu
+def test_generic_entry_refusals(ctx):
+    """what cvttmi_encode_device refuses with CVTTMI_E_INVALID before anything is queued: the poisoned output stays untouched"""
+    lib, h = ctx._lib, ctx._h
+    opt = api.Options()
+    n = 16
+    src, _ = guarded.device_input(source_blocks("ldr")[:n], 0)
+    out, check = guarded.device_buffer(n * 16, 0, 0xA5)
+    o, i, optp, planp = out.data_ptr(), src.data_ptr(), _addr(opt), _addr(_PLAN)
+    bc7, bc1 = api.TEXTURE_FORMATS["bc7"][0], api.TEXTURE_FORMATS["bc1"][0]
+    cases = [("format -1", (-1, o, i, 8, optp, planp, None, None), b"invalid argument"),
+             ("format 17", (17, o, i, 8, optp, planp, None, None), b"invalid argument"),
+             ("BC7 without a plan", (bc7, o, i, 8, optp, None, None, None), b"invalid argument"),
+             ("BC7 without options", (bc7, o, i, 8, None, planp, None, None), b"invalid argument"),
+             ("BC1 without options", (bc1, o, i, 8, None, None, None, None), b"invalid argument"),
+             ("12 blocks", (bc1, o, i, 12, optp, None, None, None), b"invalid argument"),
+             ("8-byte format, output +4", (bc1, o + 4, i, 8, optp, None, None, None), b"misaligned"),
+             ("16-byte format, output +8", (bc7, o + 8, i, 8, optp, planp, None, None), b"misaligned"),
+             ("16-byte format, input +8", (bc7, o, i + 8, 8, optp, planp, None, None), b"misaligned")]
+    for what, args, text in cases:
+        assert lib.cvttmi_encode_device(h, *args) == E_INVALID, what
+        assert text in lib.cvttmi_last_error(h), (what, lib.cvttmi_last_error(h))
+        check.untouched()
+    assert lib.cvttmi_encode_device(None, bc1, o, i, 8, optp, None, None, None) == E_INVALID  # no context: no text to keep
+    # the host entry: the same argument checks (host pointers need no alignment)
+    hsrc, _ = _host_in(source_blocks("ldr")[:n], 0)
+    hout, hcheck = guarded.host_buffer(n * 16, 0, 0xA5)
+    ho, hi = hout.ctypes.data, hsrc.ctypes.data
+    for what, args in (("format -1", (-1, ho, hi, 8, optp, planp, None)), ("format 17", (17, ho, hi, 8, optp, planp, None)),
+                       ("BC7 without a plan", (bc7, ho, hi, 8, optp, None, None)), ("BC1 without options", (bc1, ho, hi, 8, None, None, None)),
+                       ("12 blocks", (bc1, ho, hi, 12, optp, None, None))):
+        assert lib.cvttmi_encode(h, *args) == E_INVALID, what
+        assert b"invalid argument" in lib.cvttmi_last_error(h), (what, lib.cvttmi_last_error(h))
+        hcheck.untouched()
+    check.untouched()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", ["bc7", "bc6hu", "bc6hs"])
+def test_named_decoders_equal_the_generic_one(ctx, fmt):
+    """cvttmi_decode_bc7_device / cvttmi_decode_bc6h_device are cvttmi_decode_device with their id: the same bytes"""
+    lib, h = ctx._lib, ctx._h
+    fid, bpb, tex, _ = api.TEXTURE_FORMATS[fmt]
+    packed = decode_case(fmt)[0]
+    for n in GENERIC_SIZES:
+        what = "decode %s, %d blocks" % (fmt, n)
+        src, unchanged = guarded.device_input(packed[:n], bpb, what=what + ": input")
+        ref, ref_check = guarded.device_buffer(n * tex, 3 * tex, 0x5A, what=what + ": generic entry")
+        assert lib.cvttmi_decode_device(h, fid, ref.data_ptr(), src.data_ptr(), n, None) == 0, (what, lib.cvttmi_last_error(h))
+        out, check = guarded.device_buffer(n * tex, 3 * tex, 0xA5, what=what + ": named entry")
+        rc = (lib.cvttmi_decode_bc7_device(h, out.data_ptr(), src.data_ptr(), n, None) if fmt == "bc7"
+              else lib.cvttmi_decode_bc6h_device(h, out.data_ptr(), src.data_ptr(), n, 1 if fmt == "bc6hs" else 0, None))
+        assert rc == 0, (what, lib.cvttmi_last_error(h))
+        check(ref_check.payload())
+        check(_bytes(decode_case(fmt)[1]).reshape(FULL, tex)[:n])
+        unchanged()

@@ -447,7 +447,7 @@ def test_error_codes(gpu_ctx):
         assert lib.cvttmi_measure_image_error_device(h, fmt, packed.data_ptr(), src.data_ptr(), 8, 8, 64, pixels, None,
                                                      tot.data_ptr(), None) == E
     assert lib.cvttmi_measure_image_error_device(h, 1, packed.data_ptr(), src.data_ptr(), 8, 8, 16, 0, None, tot.data_ptr(), None) == E
-    # the multi-device entries reject the new ids like any unknown id
+    # the multi-device entries take every id of the table (each shard is one cvttmi_encode call) and refuse any other
     m = ctypes.c_void_p()
     devs = (ctypes.c_int * 1)(0)
     assert lib.cvttmi_multi_create(ctypes.byref(m), devs, 1) == 0
@@ -456,7 +456,10 @@ def test_error_codes(gpu_ctx):
         o = np.zeros((8, 16), np.uint8)
         opt = api.Options()
         for fid in range(6, 17):
-            assert lib.cvttmi_multi_encode(m, fid, o.ctypes.data, blocks.ctypes.data, 8, 0, ctypes.addressof(opt), None) == E
+            assert lib.cvttmi_multi_encode(m, fid, o.ctypes.data, blocks.ctypes.data, 8, 0, ctypes.addressof(opt), None) == 0, fid
+        for bad in (-1, 17, 1000):
+            assert lib.cvttmi_multi_encode(m, bad, o.ctypes.data, blocks.ctypes.data, 8, 0, ctypes.addressof(opt), None) == E, bad
+        assert lib.cvttmi_multi_encode(m, 0, o.ctypes.data, blocks.ctypes.data, 8, 0, ctypes.addressof(opt), None) == E  # BC7 without a plan
     finally:
         lib.cvttmi_multi_destroy(m)
     # the Python face

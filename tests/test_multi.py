@@ -34,9 +34,10 @@ def test_c_shard_rule_equals_the_python_one():
 
 
 @pytest.mark.gpu
-def test_multi_ragged_shards_equal_single_context(gpu_ctx, oracle_lib):
+def test_multi_ragged_shards_equal_single_context(gpu_ctx, oracle_lib, monkeypatch):
     """devices = {0,0,0}: three contexts, block rows that are no multiple of the world size and a row length that is no
     multiple of 8 blocks; every format; bytes equal the one-context call's, and BC7's equal the oracle's"""
+    monkeypatch.delenv("CVTTMI_MULTI_FORCE_STAGE", raising=False)
     m = api.MultiContext([0, 0, 0])
     rcp = oracle_lib.probe_rcp()  # this box's table: what the contexts behind the stateless forms probe for themselves
     gpu_ctx.set_rcp_table(rcp)    # (the session's context may carry the golden table of an earlier test)
@@ -55,6 +56,26 @@ def test_multi_ragged_shards_equal_single_context(gpu_ctx, oracle_lib):
     assert (m.encode("bc6hs", hdr, opt, blocks_per_row=40) == gpu_ctx.encode_bc6h(hdr, opt, signed=True)).all()
     assert (m.encode("etc2", ldr, opt, blocks_per_row=40) == gpu_ctx.encode_etc2(ldr, opt)).all()
     assert (m.encode("etc2rgba", ldr, opt, blocks_per_row=12) == gpu_ctx.encode_etc2_rgba(ldr, opt)).all()  # 12: rows end inside a group
+    # the eleven formats that go through the same generic entry per shard (R11 from its own 32-byte source blocks)
+    r11 = content.mixed_r11_blocks(95, 35)[:7 * 40]
+    for fmt in ("bc2", "bc3", "bc4u", "bc4s", "bc5u", "bc5s", "etc1", "etc2punchthrough", "eac", "r11u", "r11s"):
+        src = r11 if fmt in ("r11u", "r11s") else ldr
+        assert src.nbytes == 280 * api.MultiContext.FORMATS[fmt][1]
+        single = gpu_ctx.encode(fmt, src, opt)
+        assert single.shape == (280, api.MultiContext.FORMATS[fmt][2])
+        assert (m.encode(fmt, src, opt, blocks_per_row=40) == single).all(), fmt
+        assert m.last_shards() == [sharding.shard_block_rows(7, 40, r, 3) for r in range(3)]
+    # ... one of them device-resident, through the staged + peer-copy route (the setting is read when the handle is created)
+    import torch
+    monkeypatch.setenv("CVTTMI_MULTI_FORCE_STAGE", "1")
+    staged = api.MultiContext([0, 0, 0])
+    staged.set_rcp_table(rcp)
+    table = [sharding.shard_block_rows(7, 40, r, 3) for r in range(3)]
+    shards = [torch.from_numpy(np.ascontiguousarray(ldr[lo:hi])).cuda() for lo, hi in table]
+    out = torch.full((280, 16), 0xEE, dtype=torch.uint8, device="cuda")
+    staged.encode_device("bc5s", shards, out, blocks_per_row=40, options=opt)
+    assert (out.cpu().numpy() == gpu_ctx.encode("bc5s", ldr, opt)).all()
+    monkeypatch.delenv("CVTTMI_MULTI_FORCE_STAGE")
     # fewer rows than devices: empty shards
     two = ldr[:16]
     assert (api.MultiContext([0, 0, 0, 0, 0]).encode("bc7", two, opt, plan, blocks_per_row=8) == gpu_ctx.encode_bc7(two, opt, plan)).all()
