@@ -198,6 +198,7 @@ _EXPORTS = (
     "cvttmi_encode_bc7_multi", "cvttmi_encode_bc1_multi", "cvttmi_encode_bc6h_multi", "cvttmi_encode_etc2_rgba_multi",
     "cvttmi_dropin_set_devices",
     "cvttmi_format_info", "cvttmi_encode_device", "cvttmi_encode",
+    "cvttmi_mip_level_count", "cvttmi_mip_layout", "cvttmi_build_mips_device",
 )
 
 _lib = None
@@ -282,6 +283,11 @@ def load_library():
                                              ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     lib.cvttmi_compact_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                                ctypes.c_uint32, ctypes.c_void_p]
+    lib.cvttmi_mip_level_count.restype = ctypes.c_uint32
+    lib.cvttmi_mip_level_count.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    lib.cvttmi_mip_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    lib.cvttmi_build_mips_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]
     lib.cvttmi_decode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
@@ -344,6 +350,45 @@ TEXTURE_FORMATS = {
     "bc5s": (11, 16, 64, 0x3), "etc1": (12, 8, 64, 0x7), "etc2punchthrough": (13, 8, 64, 0xF), "eac": (14, 8, 64, 0x8),
     "r11u": (15, 8, 32, 0x1), "r11s": (16, 8, 32, 0x1),
 }
+
+
+# pixel kinds (include/cvtt_mi355x.h CVTTMI_PIXELS_*); the SNORM kind exists for the mip filter alone
+PIXELS_RGBA8, PIXELS_RGBA16F, PIXELS_RGBA8_SNORM = 0, 1, 2
+
+
+class MipLevel(ctypes.Structure):
+    """byte image of cvttmi_mip_level: a level's size and its place in the pyramid, the tiled and the packed buffer"""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("byteOffset", ctypes.c_size_t),
+                ("rowPitchBytes", ctypes.c_size_t), ("firstTile", ctypes.c_size_t), ("tileCount", ctypes.c_size_t),
+                ("firstBlock", ctypes.c_size_t), ("blockCount", ctypes.c_size_t), ("packedByteOffset", ctypes.c_size_t)]
+
+
+class MipLayout(list):
+    """cvttmi_mip_layout: a list of MipLevel, one per level, with the three totals -- bytes of the pyramid (levels 1..), blocks
+    of the tiled buffer, blocks of the packed output"""
+    pyramid_bytes = tile_count = block_count = 0
+
+
+def mip_level_count(width, height):
+    """cvttmi_mip_level_count: levels of the full chain down to 1x1; 0 when a size is 0"""
+    return int(load_library().cvttmi_mip_level_count(int(width), int(height)))
+
+
+def mip_layout(width, height, pixel_bytes, bytes_per_block, levels=None):
+    """cvttmi_mip_layout for an image of `pixel_bytes` per texel (4 = RGBA8, 8 = RGBA16F) and a format of `bytes_per_block`;
+    levels: None = the full chain.  Needs no device."""
+    lib = load_library()
+    levels = mip_level_count(width, height) if levels is None else int(levels)
+    kind = {4: PIXELS_RGBA8, 8: PIXELS_RGBA16F}.get(pixel_bytes, -1)
+    table = (MipLevel * (max(levels, 0) + 1))()
+    rc = lib.cvttmi_mip_layout(int(width), int(height), kind, int(bytes_per_block), max(levels, 0), table)
+    if rc != 0:
+        raise CvttError("cvttmi_mip_layout(%d x %d, %d bytes per texel, %d bytes per block, %d levels) failed (%d)"
+                        % (width, height, pixel_bytes, bytes_per_block, levels, rc))
+    out = MipLayout(table[:levels])
+    end = table[levels]
+    out.pyramid_bytes, out.tile_count, out.block_count = int(end.byteOffset), int(end.firstTile), int(end.firstBlock)
+    return out
 
 
 class ErrorTotals(ctypes.Structure):
@@ -785,16 +830,9 @@ class Context:
         strided -> (ceil(H/4) * ceil(ceil(W/4)/8)*8, 16, 4) PixelBlock tensor: groups of eight
         horizontally adjacent blocks, reads clamped at the right / bottom edge."""
         import torch
-        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 3 and image.shape[2] == 4):
-            raise CvttError("image must be a CUDA tensor of shape (H, W, 4)")
-        if image.device.index != self.device:
-            raise CvttError("image lives on cuda:%d but this context was created for cuda:%d" % (image.device.index, self.device))
-        if image.stride(2) != 1 or image.stride(1) != 4:
-            image = image.contiguous()
+        image = self._image_in(image)
         h, w = int(image.shape[0]), int(image.shape[1])
         esz = image.element_size()
-        if esz not in (1, 2):
-            raise CvttError("image must be RGBA8 or RGBA16F")
         n = self._lib.cvttmi_tiled_block_count(w, h)
         blocks = torch.empty((n, 16, 4), dtype=image.dtype, device=image.device)
         if stream is None:
@@ -826,6 +864,65 @@ class Context:
             raise CvttError("unknown format %r" % (fmt,))
         packed = self.encode(fmt, blocks, options, plan, stream=stream)
         return packed if w % 32 == 0 else self.compact_rows(packed, w, h, stream)
+
+    def _image_in(self, image):
+        """the (H, W, 4) image of tile_image / build_mips, texels contiguous (rows may be strided)"""
+        import torch
+        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 3 and image.shape[2] == 4):
+            raise CvttError("image must be a CUDA tensor of shape (H, W, 4)")
+        if image.device.index != self.device:
+            raise CvttError("image lives on cuda:%d but this context was created for cuda:%d" % (image.device.index, self.device))
+        if image.element_size() not in (1, 2):
+            raise CvttError("image must be RGBA8 or RGBA16F")
+        return image if image.stride(2) == 1 and image.stride(1) == 4 else image.contiguous()
+
+    # -- mip chains: 2x2 box filter on the device, and the whole chain through one encode call --
+    def build_mips(self, image, levels=None, signed=False, stream=None):
+        """(H,W,4) CUDA image -> the list of its mip levels (cvttmi_build_mips_device): [0] is the image itself, the others are
+        (h_L, w_L, 4) views of the image's dtype into ONE allocation laid out by mip_layout.  Level L+1 is max(1, w_L >> 1) x
+        max(1, h_L >> 1), a 2x2 box of the rounded level L (an odd last row / column is dropped).  uint8: (a+b+c+d+2) >> 2;
+        int8, or signed=True (the bytes BC4S / BC5S read): the same on int8 with an arithmetic shift; a 2-byte dtype: RGBA16F,
+        ((a+b)+(c+d)) * 0.25 in float, rounded to nearest even.  levels: None = the full chain down to 1x1."""
+        import torch
+        image = self._image_in(image)
+        h, w = int(image.shape[0]), int(image.shape[1])
+        esz = image.element_size()
+        if esz == 2 and signed:
+            raise CvttError("signed selects the int8 rule of an RGBA8 image")
+        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or image.dtype == torch.int8) else PIXELS_RGBA8
+        layout = mip_layout(w, h, 4 * esz, 16, levels)
+        pyramid = torch.empty(layout.pyramid_bytes, dtype=torch.uint8, device=image.device)
+        stream = self._stream(stream, image.device)
+        self._check(self._lib.cvttmi_build_mips_device(self._h, pyramid.data_ptr(), layout.pyramid_bytes, image.data_ptr(), w, h,
+                                                       image.stride(0) * esz, kind, len(layout), ctypes.c_void_p(stream)), "build_mips")
+        return [image] + [pyramid[L.byteOffset: L.byteOffset + L.rowPitchBytes * L.height].view(image.dtype).view(L.height, L.width, 4)
+                          for L in layout[1:]]
+
+    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None):
+        """(H,W,4) CUDA image -> the packed blocks of every mip level: a list of (ceil(w_L/4) * ceil(h_L/4), bytes per block)
+        uint8 views, level 0 first, consecutive in one allocation (container order).  Level L equals
+        encode_image(fmt, build_mips(image)[L]) byte for byte; the levels are tiled into one block tensor and searched by ONE
+        encode call (groups of eight blocks are independent), so the small levels cost no launches of their own.  fmt as for
+        encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain."""
+        import torch
+        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
+            raise CvttError("unknown format %r" % (fmt,))
+        _, bpb, _, _ = TEXTURE_FORMATS[fmt]
+        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream)
+        image = images[0]
+        esz = image.element_size()
+        layout = mip_layout(int(image.shape[1]), int(image.shape[0]), 4 * esz, bpb, len(images))
+        sp = ctypes.c_void_p(self._stream(stream, image.device))
+        blocks = torch.empty((layout.tile_count, 16, 4), dtype=image.dtype, device=image.device)
+        for L, img in zip(layout, images):
+            self._check(self._lib.cvttmi_tile_image_device(self._h, blocks[L.firstTile:].data_ptr(), img.data_ptr(), L.width, L.height,
+                                                           img.stride(0) * esz, 0 if esz == 1 else 1, sp), "tile_image")
+        packed = self.encode(fmt, blocks, options, plan, stream=stream)
+        out = torch.empty((layout.block_count, bpb), dtype=torch.uint8, device=image.device)
+        for L in layout:
+            self._check(self._lib.cvttmi_compact_rows_device(self._h, out[L.firstBlock:].data_ptr(), packed[L.firstTile:].data_ptr(),
+                                                             L.width, L.height, bpb, sp), "compact_rows")
+        return [out[L.firstBlock: L.firstBlock + L.blockCount] for L in layout]
 
 
 _default_ctx = {}

@@ -121,3 +121,91 @@ def read_dds(path_or_bytes):
     n = ((width + 3) // 4) * ((height + 3) // 4)
     blocks = np.frombuffer(raw, np.uint8, n * per, 148).reshape(n, per).copy()
     return names[0], width, height, blocks
+
+
+# ---- mip chains: level 0 first in both containers, so read_ktx / read_dds above return level 0 of these files ----
+
+def mip_sizes(width, height, levels):
+    """[(w_L, h_L)] of the first `levels` levels: each max(1, previous >> 1); at most floor(log2(max(w, h))) + 1 of them"""
+    full = max(int(width), int(height), 1).bit_length()
+    if width < 1 or height < 1 or not 1 <= levels <= full:
+        raise ValueError("a %dx%d texture has 1 .. %d mip levels, got %d" % (width, height, full, levels))
+    return [(max(1, width >> l), max(1, height >> l)) for l in range(levels)]
+
+
+def _mip_payloads(fmt, width, height, levels):
+    levels = list(levels)
+    return [_payload(fmt, w, h, packed) for (w, h), packed in zip(mip_sizes(width, height, len(levels)), levels)]
+
+
+def ktx_mips_bytes(fmt, width, height, levels):
+    """KTX 1.1 with numberOfMipmapLevels = len(levels): per level a uint32 imageSize and its blocks (what
+    Context.encode_mips returns, level 0 first).  Blocks are 8 or 16 bytes, so the mip padding to 4 bytes is always empty."""
+    fmt = canonical(fmt)
+    data = _mip_payloads(fmt, width, height, levels)
+    _, internal, base, _ = FORMATS[fmt]
+    header = _KTX_ID + struct.pack("<13I", 0x04030201, 0, 1, 0, internal, base, width, height, 0, 0, 1, len(data), 0)
+    return header + b"".join(struct.pack("<I", d.size) + d.tobytes() for d in data)
+
+
+def write_ktx_mips(path, fmt, width, height, levels):
+    with open(path, "wb") as f:
+        f.write(ktx_mips_bytes(fmt, width, height, levels))
+
+
+def read_ktx_mips(path_or_bytes):
+    """-> (format name, width, height, [blocks (N_L, bytesPerBlock) uint8 per level])"""
+    raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+    name, width, height, _ = read_ktx(raw)
+    count, kv = struct.unpack_from("<2I", raw, 12 + 4 * 11)
+    per = FORMATS[name][0]
+    off, levels = 64 + kv, []
+    for w, h in mip_sizes(width, height, max(1, count)):
+        size, = struct.unpack_from("<I", raw, off)
+        if size != ((w + 3) // 4) * ((h + 3) // 4) * per:
+            raise ValueError("mip level %d (%dx%d) holds %d bytes" % (len(levels), w, h, size))
+        levels.append(np.frombuffer(raw, np.uint8, size, off + 4).reshape(-1, per).copy())
+        off += 4 + (size + 3) // 4 * 4
+    return name, width, height, levels
+
+
+def dds_mips_bytes(fmt, width, height, levels):
+    """DDS (DX10 header) with dwMipMapCount = len(levels): the levels' blocks one after the other behind the headers.  More
+    than one level sets DDSD_MIPMAPCOUNT and DDSCAPS_COMPLEX | DDSCAPS_MIPMAP; pitchOrLinearSize is level 0's size."""
+    fmt = canonical(fmt)
+    dxgi = FORMATS[fmt][3]
+    if dxgi is None:
+        raise ValueError("%s has no DXGI format; use KTX" % fmt)
+    data = _mip_payloads(fmt, width, height, levels)
+    flags = 0x1 | 0x2 | 0x4 | 0x1000 | 0x80000  # DDSD_CAPS | HEIGHT | WIDTH | PIXELFORMAT | LINEARSIZE
+    caps = 0x1000  # DDSCAPS_TEXTURE
+    if len(data) > 1:
+        flags |= 0x20000  # DDSD_MIPMAPCOUNT
+        caps |= 0x8 | 0x400000  # DDSCAPS_COMPLEX | DDSCAPS_MIPMAP
+    pixel_format = struct.pack("<2I4s5I", 32, 0x4, b"DX10", 0, 0, 0, 0, 0)  # DDPF_FOURCC
+    header = struct.pack("<7I", 124, flags, height, width, data[0].size, 0, len(data)) + bytes(44) + pixel_format + \
+        struct.pack("<5I", caps, 0, 0, 0, 0)
+    dx10 = struct.pack("<5I", dxgi, 3, 0, 1, 0)  # D3D10_RESOURCE_DIMENSION_TEXTURE2D, array size 1
+    return _DDS_MAGIC + header + dx10 + b"".join(d.tobytes() for d in data)
+
+
+def write_dds_mips(path, fmt, width, height, levels):
+    with open(path, "wb") as f:
+        f.write(dds_mips_bytes(fmt, width, height, levels))
+
+
+def read_dds_mips(path_or_bytes):
+    """-> (format name, width, height, [blocks per level]); a file without DDSD_MIPMAPCOUNT has one level"""
+    raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+    name, width, height, _ = read_dds(raw)
+    flags, = struct.unpack_from("<I", raw, 8)
+    count, = struct.unpack_from("<I", raw, 28)
+    per = FORMATS[name][0]
+    off, levels = 148, []
+    for w, h in mip_sizes(width, height, max(1, count) if flags & 0x20000 else 1):
+        n = ((w + 3) // 4) * ((h + 3) // 4)
+        if off + n * per > len(raw):
+            raise ValueError("mip level %d (%dx%d) is cut short" % (len(levels), w, h))
+        levels.append(np.frombuffer(raw, np.uint8, n * per, off).reshape(n, per).copy())
+        off += n * per
+    return name, width, height, levels

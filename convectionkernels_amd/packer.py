@@ -1,6 +1,6 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-metrics] input output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-metrics] input output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
@@ -9,7 +9,11 @@ edge clamping (etc2packer.cpp:215-248), encoding and the removal of padding bloc
 packed blocks are already in container order.  The input is anything PIL opens, or a .npy of shape (H, W, 4) uint8.
 -metrics: after the file is written, print the encoding error to stdout, measured on the device against the input image
 (Context.measure_image: one line per measured channel with its MSE and PSNR, then the PSNR over all of them; R11 has no
-image form and is measured over the written blocks against their tiles, the clamped texels of the edge blocks included)."""
+image form and is measured over the written blocks against their tiles, the clamped texels of the edge blocks included).
+-mips: the file holds the full mip chain down to 1x1 (Context.encode_mips: 2x2 box filter on the device, floor convention, every
+level from the rounded one before it, all levels searched by one encode call).  With -metrics the lines of level 0 come first,
+unchanged, then one line per further level: its PSNR over the format's channels against that level's own image.  Not for
+R11, which has no image form."""
 import sys
 
 import numpy as np
@@ -60,6 +64,25 @@ def encode_file(image, fmt, options=None, plan=None, ctx=None):
     return packed.cpu().numpy()
 
 
+def encode_file_mips(image, fmt, options=None, plan=None, ctx=None):
+    """(H, W, 4) uint8 numpy image -> [packed blocks of level L], the full chain, container order (not R11)"""
+    import torch
+    ctx = ctx or api.default_context()
+    levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan)
+    torch.cuda.synchronize(ctx.device)
+    return [level.cpu().numpy() for level in levels]
+
+
+def measure_file_mips(image, fmt, levels, ctx=None):
+    """[ErrorReport of level L against its own image] for the levels encode_file_mips returned, level 0 left out"""
+    import torch
+    ctx = ctx or api.default_context()
+    fmt = container.canonical(fmt)
+    images = ctx.build_mips(torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device), len(levels), signed=fmt in ("bc4s", "bc5s"))
+    return [ctx.measure_image(fmt, img, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
+            for img, packed in zip(images[1:], levels[1:])]
+
+
 def measure_file(image, fmt, packed, options=None, ctx=None):
     """ErrorReport of the packed blocks encode_file returned for `image`"""
     import torch
@@ -93,7 +116,7 @@ def print_metrics(report, out=None):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    fmt, uniform, fake, quality, dds, metrics, paths = "etc2rgb", False, False, None, False, False, []
+    fmt, uniform, fake, quality, dds, metrics, mips, paths = "etc2rgb", False, False, None, False, False, False, []
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -109,6 +132,8 @@ def main(argv=None):
             dds = True
         elif a == "-metrics":
             metrics = True
+        elif a == "-mips":
+            mips = True
         elif a == "-fakebt709":
             fake = True
         elif a.startswith("-"):
@@ -122,6 +147,8 @@ def main(argv=None):
         return 2
     try:
         fmt = container.canonical(fmt)
+        if mips and fmt in ("r11u", "r11s"):
+            raise ValueError("-mips: %s has no image form, so no mip chain" % fmt)
         image = load_rgba8(paths[0])
     except (ValueError, OSError) as e:
         sys.stderr.write("%s\n" % e)
@@ -135,11 +162,20 @@ def main(argv=None):
     if quality is not None:
         plan = api.BC7EncodingPlan()
         api.ConfigureBC7EncodingPlanFromQuality(plan, quality)
-    packed = encode_file(image, fmt, options, plan)
     h, w = image.shape[:2]
-    (container.write_dds if dds else container.write_ktx)(paths[1], fmt, w, h, packed)
+    if mips:
+        levels = encode_file_mips(image, fmt, options, plan)
+        packed = levels[0]
+        (container.write_dds_mips if dds else container.write_ktx_mips)(paths[1], fmt, w, h, levels)
+    else:
+        packed = encode_file(image, fmt, options, plan)
+        (container.write_dds if dds else container.write_ktx)(paths[1], fmt, w, h, packed)
     if metrics:
         print_metrics(measure_file(image, fmt, packed, options))
+        if mips:
+            for l, report in enumerate(measure_file_mips(image, fmt, levels), 1):
+                sys.stdout.write("mip %d %dx%d psnr %.4f dB (%s, %d texels)\n" % (l, max(1, w >> l), max(1, h >> l), report.psnr(),
+                                                                                  report.channels.upper(), report.texels))
     return 0
 
 

@@ -320,6 +320,53 @@ int cvttmi_tile_image_device(cvttmi_context *ctx, void *d_blocks, const void *d_
 int cvttmi_compact_rows_device(cvttmi_context *ctx, void *d_out, const void *d_packed, uint32_t width, uint32_t height,
                                uint32_t bytesPerBlock, void *hipStream);
 
+/* ---- mip chains (not part of the reference's API: its packer writes one level, etc2packer.cpp:116-197) ----
+ * Level 0 is the image; level L+1 is max(1, w_L >> 1) x max(1, h_L >> 1); a full chain has floor(log2(max(w, h))) + 1 levels
+ * and ends at 1x1.  cvttmi_mip_level_count gives that number (0 when a size is 0).
+ * Filter: a 2x2 box over texels (2x, 2y), (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1) of level L, coordinates clamped to w_L - 1 and
+ * h_L - 1 (that only matters when a dimension is already 1; an odd dimension drops its last column / row: the usual floor
+ * convention).  Every level is computed from the ROUNDED level before it.  Per channel:
+ *   CVTTMI_PIXELS_RGBA8        (a + b + c + d + 2) >> 2 on unsigned bytes
+ *   CVTTMI_PIXELS_RGBA8_SNORM  the same on the bytes read as int8, in int32, arithmetic shift: floor((sum + 2) / 4) -- the
+ *                              images BC4S / BC5S are encoded from.  Only the two mip calls take this constant.
+ *   CVTTMI_PIXELS_RGBA16F      half -> float, ((a + b) + (c + d)) * 0.25f in that order, -> half round-to-nearest-even.  Finite
+ *                              inputs are the contract: non-finite values propagate as IEEE arithmetic does, NaN bits unspecified.
+ * No sRGB-aware averaging, no other filter, no alpha-coverage preservation.
+ * cvttmi_mip_layout: host only, no context.  Fills out[0 .. levels - 1] with each level's place in three buffers, and
+ * out[levels] (so `out` has levels + 1 entries) with their ends = the three total sizes:
+ *   the pyramid   levels 1 .. levels-1 as images with tightly pitched rows, each level starting on a 256-byte boundary of the
+ *                 buffer (byteOffset, rowPitchBytes; both 0 for level 0, which stays where the caller has it);
+ *                 out[levels].byteOffset = bytes the pyramid needs (0 for one level)
+ *   the tiles     ONE PixelBlock buffer for all levels (firstTile, tileCount = cvttmi_tiled_block_count(w_L, h_L)): every
+ *                 level is whole groups of eight, so one cvttmi_encode_device call covers the chain;
+ *                 out[levels].firstTile = blocks of that buffer
+ *   the output    the ceil(w_L/4) x ceil(h_L/4) packed blocks of each level, levels consecutive = container order
+ *                 (firstBlock, blockCount, packedByteOffset = firstBlock x bytesPerBlock); out[levels].firstBlock = all blocks
+ * CVTTMI_E_INVALID, nothing written: NULL out, a zero size, an unknown pixel kind, bytesPerBlock not 8 or 16, levels 0 or more
+ * than cvttmi_mip_level_count, a pyramid beyond size_t.
+ * cvttmi_build_mips_device: level 1 from d_image (rowPitchBytes between rows), every later level from the one before it in
+ * d_pyramid; one launch per level on hipStream; levels == 1 launches nothing (d_pyramid may then be NULL).  Writes exactly the
+ * levels' bytes: the gaps that align a level's start are not touched.  d_image / d_pyramid: aligned to the texel (4 / 8 bytes);
+ * where the image's rows and the pyramid also start on 16-byte boundaries (any hipMalloc'ed pyramid) and a level's width is a
+ * multiple of 16 bytes, the level is made with 16-byte accesses.  CVTTMI_E_INVALID before anything is queued: NULL pointers,
+ * levels 0 or too many, pyramidBytes below out[levels].byteOffset, an unknown pixel kind, rowPitchBytes below the row or no
+ * multiple of the texel, a misaligned pointer.  Image and pyramid must not overlap.
+ * There is no entry that encodes a chain: tile every level into its slot of the tile buffer (cvttmi_tile_image_device takes a
+ * row pitch and any output offset), encode once, compact every level into its slot of the output. */
+#define CVTTMI_PIXELS_RGBA8_SNORM 2
+typedef struct cvttmi_mip_level
+{
+    uint32_t width, height;
+    size_t byteOffset, rowPitchBytes; /* in the pyramid */
+    size_t firstTile, tileCount;      /* in the tiled PixelBlock buffer, in blocks */
+    size_t firstBlock, blockCount;    /* in the packed output, in blocks */
+    size_t packedByteOffset;          /* = firstBlock x bytesPerBlock */
+} cvttmi_mip_level;
+uint32_t cvttmi_mip_level_count(uint32_t width, uint32_t height);
+int cvttmi_mip_layout(uint32_t width, uint32_t height, int pixelFormat, uint32_t bytesPerBlock, uint32_t levels, cvttmi_mip_level *out);
+int cvttmi_build_mips_device(cvttmi_context *ctx, void *d_pyramid, size_t pyramidBytes, const void *d_image, uint32_t width,
+                             uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, void *hipStream);
+
 /* BC2 / BC3 / BC4 / BC5: cvtt::Kernels::EncodeBC2, EncodeBC3, EncodeBC4U/S, EncodeBC5U/S (reference
  * ConvectionKernels_API.cpp:101-199 -> S3TCComputer::PackRGB without alpha test, PackExplicitAlpha,
  * PackInterpolatedAlpha, ConvectionKernels_S3TC.cpp:306-715).  Input PixelBlockU8 (isSigned: PixelBlockS8, biased
