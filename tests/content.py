@@ -347,3 +347,228 @@ def adversarial_bound_blocks(seed, n):
     one = (av == 1) & (rng.integers(0, 16, groups * 8) == 0)
     out[one, 5, 3] = 200
     return np.ascontiguousarray(out.astype(np.uint8))
+
+
+# ---- directed content: blocks built so that a chosen encoding wins (tests/test_mode_census.py proves that it did) ----
+
+def partition_shaped_blocks(subsets, alpha, seed, per=8):
+    """(64 * per, 16, 4) uint8: one group of `per` blocks per BC7 partition of the two- or three-subset table
+    (tools/gen_tables.py P2 / P3; mode 0 uses the first 16 three-subset groups).  The pixels of each subset lie on their own
+    random colour line, so the partition the block was shaped after beats every other one; odd blocks carry +-1 LSB noise.
+    alpha: False = 255 everywhere, True = alpha follows the line of its subset."""
+    from tools import gen_tables
+    assert subsets in (2, 3)
+    rng = _rng(seed)
+    out = np.zeros((64 * per, 16, 4), np.uint8)
+    px = np.arange(16)
+    for part in range(64):
+        if subsets == 2:
+            owner = (gen_tables.P2[part] >> px) & 1
+        else:
+            owner = (gen_tables.P3[part] >> (2 * px)) & 3
+        for b in range(per):
+            v = np.zeros((16, 4), np.float64)
+            for s in range(subsets):
+                lo = rng.integers(0, 256, 4).astype(np.float64)
+                hi = rng.integers(0, 256, 4).astype(np.float64)
+                t = rng.random(16)
+                t[rng.integers(0, 16)] = 0.0
+                t[rng.integers(0, 16)] = 1.0
+                line = lo[None, :] + (hi - lo)[None, :] * t[:, None]
+                v = np.where((owner == s)[:, None], line, v)
+            if b & 1:
+                v = v + rng.integers(-1, 2, (16, 4))
+            blk = np.clip(np.rint(v), 0, 255)
+            if not alpha:
+                blk[:, 3] = 255
+            out[part * per + b] = blk
+    return out
+
+
+def dual_plane_blocks(seed, per=16):
+    """(8 * per, 16, 4) uint8 for BC7 modes 4 and 5: one channel (the rotation: alpha, red, green, blue) varies independently
+    of the other three, which share a line.  Groups alternate between a wide scalar range with a narrow colour range and the
+    reverse, which is what separates the two index selectors of mode 4."""
+    rng = _rng(seed)
+    out = np.zeros((8 * per, 16, 4), np.uint8)
+    for g in range(8):
+        lone = (3, 0, 1, 2)[g % 4]
+        for b in range(per):
+            lo = rng.integers(0, 256, 4).astype(np.float64)
+            hi = rng.integers(0, 256, 4).astype(np.float64)
+            if g >= 4:   # narrow scalar, wide colour
+                hi[lone] = np.clip(lo[lone] + rng.integers(-24, 25), 0, 255)
+            else:        # wide scalar, narrow colour
+                for c in range(4):
+                    if c != lone:
+                        hi[c] = np.clip(lo[c] + rng.integers(-24, 25), 0, 255)
+            t = rng.random(16)
+            u = rng.random(16)
+            v = lo[None, :] + (hi - lo)[None, :] * t[:, None]
+            v[:, lone] = lo[lone] + (hi[lone] - lo[lone]) * u
+            if b & 1:
+                v = v + rng.integers(-1, 2, (16, 4))
+            out[g * per + b] = np.clip(np.rint(v), 0, 255)
+    return out
+
+
+BC6H_SPREADS = (32, 64, 128, 256, 512, 1024, 2048, 4096, 16384)
+BC6H_EMPHASIS = ((1, 1, 1), (1, 2, 1), (2, 1, 1), (1, 1, 2))
+
+
+def bc6h_mode_blocks(signed, seed):
+    """(N, 16, 4) int16 half bit patterns, N a multiple of 8: partition-shaped two-line HDR blocks for the 32 BC6H partitions
+    plus the whole block (index 32), built in half-bit-pattern space.  For every shape the endpoint spread sweeps BC6H_SPREADS
+    units (the width of the line inside a subset AND the distance between the subsets' base values, which is what the delta
+    fields of the transformed modes have to hold) and the channel emphasis BC6H_EMPHASIS scales one channel's spread by two
+    (and, in the second half of the variants, the other two down by four), so that one channel's delta budget binds while the
+    others stay inside theirs: modes 6, 10, 22 and 26 against 2, 18 and 14.  Base values lie in 0x1000..0x6000; signed content
+    carries sign bits on odd blocks.  A second, aimed family follows (384 blocks): per partition, base precision (11 and 8
+    bits) and channel, the one channel's delta sits between 8 and 15 quantisation steps and the other two below 7."""
+    from tools import gen_tables
+    rng = _rng(seed)
+    px = np.arange(16)
+    blocks = []
+    for shape in range(33):
+        owner = (gen_tables.P2[shape] >> px) & 1 if shape < 32 else np.zeros(16, np.int64)
+        for si, spread in enumerate(BC6H_SPREADS):
+            for ei, emph in enumerate(BC6H_EMPHASIS):
+                for variant in range(2):
+                    e = np.array(emph, np.float64)
+                    if variant:
+                        e = np.where(e > 1, 2.0, 0.25) if ei else np.array([1.0, 0.25, 0.0625])
+                    base = rng.integers(0x1000, 0x6000, 3).astype(np.float64)
+                    v = np.zeros((16, 3), np.float64)
+                    for s in range(2):
+                        # the second subset sits `spread` away from the first: the delta of its endpoints
+                        off = (rng.random(3) * 2 - 1) * spread * e * (2.0 if s else 0.0)
+                        width = (rng.random(3) * 2 - 1) * spread * e * (1.0 if variant == 0 else 0.5)
+                        t = rng.random(16)
+                        line = base[None, :] + off[None, :] + width[None, :] * t[:, None]
+                        v = np.where((owner == s)[:, None], line, v)
+                    v = np.clip(np.rint(v), 0, 0x7BFF).astype(np.int64)
+                    if signed and (len(blocks) & 1):
+                        neg = rng.integers(0, 3)
+                        if neg == 0:      # whole block negative
+                            v |= 0x8000
+                        elif neg == 1:    # one subset negative
+                            v |= (owner[:, None] << 15)
+                        else:             # small values straddling zero
+                            v = (v & 0x3FF) | (rng.integers(0, 2, (16, 1)) << 15)
+                    blk = np.zeros((16, 4), np.int64)
+                    blk[:, :3] = v
+                    blk[:, 3] = 0x3C00
+                    blocks.append(blk)
+    # the one-channel-binds modes again, aimed: the delta of the emphasised channel between 8 and 15 steps of the mode's base
+    # precision (11 bits: 32 units a step; 8 bits: 256), the other two below 7 steps
+    for shape in range(32):
+        owner = (gen_tables.P2[shape] >> px) & 1
+        for step in (32, 256):
+            for ch in range(3):
+                for variant in range(2):
+                    base = rng.integers(0x1800, 0x5800, 3).astype(np.float64)
+                    reach = np.full(3, 5.0 if variant else 3.0) * step
+                    reach[ch] = (13.0 if variant else 10.0) * step
+                    v = np.zeros((16, 3), np.float64)
+                    for s in range(2):
+                        off = rng.choice(np.array([-1.0, 1.0]), 3) * reach * (0.9 if s else 0.0)
+                        width = rng.choice(np.array([-1.0, 1.0]), 3) * reach * 0.8
+                        t = rng.random(16)
+                        t[rng.integers(0, 16)] = 0.0
+                        t[rng.integers(0, 16)] = 1.0
+                        line = base[None, :] + off[None, :] + width[None, :] * t[:, None]
+                        v = np.where((owner == s)[:, None], line, v)
+                    v = np.clip(np.rint(v), 0, 0x7BFF).astype(np.int64)
+                    if signed and variant:
+                        v |= 0x8000
+                    blk = np.zeros((16, 4), np.int64)
+                    blk[:, :3] = v
+                    blk[:, 3] = 0x3C00
+                    blocks.append(blk)
+    out = np.array(blocks, np.uint16)
+    assert len(out) % 8 == 0
+    return out.view(np.int16)
+
+
+ETC_AMPLITUDES = (0, 3, 6, 10, 16, 24, 40, 64)
+
+
+def etc_half_blocks(seed, reps=2):
+    """(2 * 64 * reps * 2, 16, 4) uint8: two half-blocks along either flip with different base colours and independent luma
+    amplitudes from ETC_AMPLITUDES (the small modifier of the eight tables; the pixels sit at +-1 and +-3 amplitudes, the
+    shape of every table), one group per table codeword pair; three repetitions in four keep the bases within the
+    differential range of each other, the fourth does not (individual / T / H territory).  Alpha: 255, with a transparent
+    pixel or half in one block of eight (the punch-through encoder reads it; the others ignore it)."""
+    rng = _rng(seed)
+    out = []
+    yy, xx = np.divmod(np.arange(16), 4)
+    for flip in range(2):
+        half = (yy >= 2) if flip else (xx >= 2)
+        for a0 in ETC_AMPLITUDES:
+            for a1 in ETC_AMPLITUDES:
+                for r in range(reps * 2):
+                    b0 = rng.integers(40, 216, 3).astype(np.float64)
+                    if r % 4:
+                        b1 = np.clip(b0 + rng.integers(-24, 25, 3), 0, 255)
+                    else:
+                        b1 = rng.integers(40, 216, 3).astype(np.float64)
+                    amp = np.where(half, a1, a0).astype(np.float64)
+                    luma = rng.choice(np.array([-3.0, -1.0, 1.0, 3.0]), 16) * amp
+                    v = np.where(half[:, None], b1[None, :], b0[None, :]) + luma[:, None]
+                    blk = np.full((16, 4), 255, np.int64)
+                    blk[:, :3] = np.clip(np.rint(v), 0, 255)
+                    k = len(out) % 8
+                    if k == 3:
+                        blk[rng.integers(0, 16), 3] = 0
+                    elif k == 6:
+                        blk[half, 3] = 0
+                    out.append(blk)
+    return np.array(out, np.uint8)
+
+
+def eac_directed_blocks(seed, per=4):
+    """(16 * 16 * per, 16) int16: for every EAC (multiplier, table) pair, `per` blocks whose values are the reconstruction
+    base + modifier * multiplier of that pair (tests/texture_decode_ref.py EAC_MODIFIERS) with every modifier present, in
+    8-bit alpha units 0..255.  Multiplier 0 rows are flat or two-valued narrow blocks.  Scale with `eac_to_r11`."""
+    import texture_decode_ref as R
+    rng = _rng(seed)
+    out = np.zeros((16 * 16 * per, 16), np.int16)
+    i = 0
+    for mult in range(16):
+        for table in range(16):
+            mods = R.EAC_MODIFIERS[table]
+            reach = max(1, mult) * int(np.abs(mods).max())
+            for b in range(per):
+                lo, hi = min(reach, 127), max(255 - reach, 128)
+                base = int(rng.integers(lo, hi + 1))
+                pick = np.concatenate([np.arange(8), rng.integers(0, 8, 8)])
+                rng.shuffle(pick)
+                v = base + mods[pick] * mult
+                if b & 1 and mult:
+                    v = v + rng.integers(-1, 2, 16) * (mult // 3)
+                out[i] = np.clip(v, 0, 255)
+                i += 1
+    return out
+
+
+def eac_to_r11(values, signed):
+    """8-bit-unit content -> the R11 input range: 0..2047, or -1023..1023; odd blocks get sub-step noise (multiplier 0 is the
+    only one that can follow it)"""
+    v = values.astype(np.int32) * 8 + 4
+    rng = _rng(len(values))
+    noise = rng.integers(-3, 4, v.shape)
+    noise[::2] = 0
+    v = v + noise
+    if signed:
+        v = v - 1024
+        return np.clip(v, -1023, 1023).astype(np.int16)
+    return np.clip(v, 0, 2047).astype(np.int16)
+
+
+def r11_narrow_blocks(seed, n, signed):
+    """(n, 16) int16: ranges of a few units around a base -- where EAC R11 takes multiplier 0 (steps of 1 / 8 of the others')"""
+    rng = _rng(seed)
+    lo, hi = (-1023, 1023) if signed else (0, 2047)
+    base = rng.integers(lo + 20, hi - 20, (n, 1))
+    width = rng.integers(1, 16, (n, 1))
+    return np.clip(base + rng.integers(-15, 16, (n, 16)) * width // 15, lo, hi).astype(np.int16)

@@ -7,6 +7,8 @@ Outputs (data only -- inputs, expected outputs, the generating host's RCPPS tabl
     tests/golden/bc7_mixed.npz      mixed-content groups x option/plan variants
     tests/golden/known_answers.npz  SURVEY.md App. H group (BC7/BC1/ETC2RGBA/BC6HU)
     tests/golden/config_hashes.json SHA-256 of whole-image outputs for the BASELINE configs
+    tests/golden/mode_census.npz    the directed cases of tests/census_cases.py (every mode / partition / layout);
+                                    `--only-mode-census` writes this file alone
 """
 import hashlib
 import json
@@ -60,10 +62,33 @@ def parallel_encode(fn, blocks, per_out, threads=8):
     return out
 
 
+def mode_census(ref, fast, rcp):
+    """tests/golden/mode_census.npz: the reference's packed output on every directed case (inputs are regenerated from
+    their seeds by tests/census_cases.py), with the options and plan bytes and the RCPPS table"""
+    import census_cases
+    arrays = {"rcp": rcp}
+    names = []
+    for case in census_cases.all_cases():
+        name, kind, _, ob, pb = case
+        out = census_cases.encode_reference(ref, case)
+        if kind == "bc7":
+            assert (out == census_cases.encode_reference(fast, case)).all(), name  # BC7 is build-stable
+            arrays["plan_" + name] = pb
+        arrays["opt_" + name] = ob
+        arrays["out_" + name] = out
+        names.append(name)
+    arrays["names"] = np.array(names)
+    np.savez_compressed(os.path.join(HERE, "mode_census.npz"), **arrays)
+
+
 def main():
     ref = pyref.RefLib()
     fast = pyref.RefLib(fast=True)
     rcp = ref.probe_rcp()
+
+    mode_census(ref, fast, rcp)
+    if "--only-mode-census" in sys.argv:
+        return
 
     # ---- mixed content x variants ----
     blocks = content.mixed_ldr_blocks(20260929, 24)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import texture_decode_ref as R
+from block_fields import etc_modes as _etc_modes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -104,21 +105,6 @@ def test_numpy_restatement_against_pillow():
                 # (six-level index 6 of a signed block is -1.0: the reference reads it as -127, Pillow as -128)
                 exact = (idx <= 1) | (six & (idx >= (7 if fmt == "bc5s" else 6)))
                 assert (diff[:, :, chans.index(ch) if fmt.startswith("bc5") else ch][exact] == 0).all(), fmt
-
-
-def _etc_modes(bc, off=0, punchthrough=False):
-    w = R._be64(bc, off)
-    diff = R._bits(w, 33, 1) == 1
-    differential = np.ones(len(bc), bool) if punchthrough else diff
-
-    def over(s5, s3):
-        v = R._bits(w, s5, 5) + np.where(R._bits(w, s3, 3) >= 4, R._bits(w, s3, 3) - 8, R._bits(w, s3, 3))
-        return (v < 0) | (v > 31)
-    t = differential & over(59, 56)
-    h = differential & ~t & over(51, 48)
-    p = differential & ~t & ~h & over(43, 40)
-    return {"individual": ~differential, "differential": differential & ~t & ~h & ~p, "T": t, "H": h, "planar": p,
-            "opaque0": punchthrough & ~diff & ~p}
 
 
 def test_random_fixtures_cover_every_mode():
