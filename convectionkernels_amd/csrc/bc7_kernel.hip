@@ -1281,8 +1281,16 @@ __device__ __forceinline__ void evalDualFast(const u32 *sP, const DualInv &inv, 
                     const v2f p01 = (x01 - org01) * ax01, p23 = (x23 - org23) * ax23;
                     float dist = p01.x + p01.y;
                     dist = dist + p23.x;
-                    const float fRGB = clampRound(dist, rgbMax);
-                    const float fA = clampRound(p23.y, alphaMaxV);
+                    // clampRound in two halves.  The last round's index goes to v_cvt_pk_u8_f32 alone, which rounds to nearest even
+                    // and saturates at 0 itself: the upper clamp is all it needs (clampHigh, cvtt_kernel_common.h).  The other
+                    // rounds' index also weights the refiner and takes the rest: clampRound(v, hi) = rintf(fmaxf(clampHigh(v, hi), 0)).
+                    float fRGB = clampHigh(dist, rgbMax);
+                    float fA = clampHigh(p23.y, alphaMaxV);
+                    if (!last)
+                    {
+                        fRGB = rintf(fmaxf(fRGB, 0.0f));
+                        fA = rintf(fmaxf(fA, 0.0f));
+                    }
                     // the indexes are small integers: v_cvt_pk_u8_f32 converts and files one as byte k in one instruction
                     iR4 = __builtin_amdgcn_cvt_pk_u8_f32(fRGB, (u32)k, iR4);
                     iA4 = __builtin_amdgcn_cvt_pk_u8_f32(fA, (u32)k, iA4);
@@ -2148,11 +2156,17 @@ __device__ __forceinline__ void maskedSums(const Proj2D<G8> &P, u32 mask, Sums2D
 // Lower bound on the error of any trial of the subset with sums `m`.  |coordinates| <= 2040 and
 // n <= 16 keep n*sum(uu) and sum(u)^2 below 2^31, so A, B, C are exact; the float steps that
 // follow are protected by relative margins on the large terms.
+// Straight-line code (no branch, no exec-mask region: 1 024 of these run per wave and stage set):
+//   * a subset of fewer than two pixels has a = b = c = 0 exactly, hence lam = L = 0 and lb = 0 (rcpN of an empty subset is
+//     0, a finite value);
+//   * lam slightly below zero (collinear or single-colour subsets, from the margins) is clamped to 0 ahead of the square root,
+//     so no NaN is formed and lb = 0;
+//   * for 0 <= L <= n^2 delta^2, where the bound is void, L/n - 2 delta sqrt(L) = s (s/n - 2 delta) with s = sqrt(L) <= n delta
+//     is at most -s delta: the two terms differ by a factor of two or more, far beyond any rounding, and the closing max gives 0.
+// `rcpN` = 1/n rounded toward zero (kRcpDown, cvtt_kernel_common.h): L * rcpN never exceeds L/n.
 template <bool G8 = false>
-__device__ __forceinline__ float subsetBound2D(const Sums2D &m, float invScaleSq, float delta)
+__device__ __forceinline__ float subsetBound2D(const Sums2D &m, float rcpN, float invScaleSq, float twoDelta)
 {
-    if (m.n < 2)
-        return 0.0f;
     // |sum u|, |sum v| <= 16 * 2040 fit 24 bits: v_mul_i32_i24 is a full-rate instruction, v_mul_lo_u32 is not; on the 8-bit
     // grid the sums of squares (<= 16 * 128^2) fit as well
     const int a = (G8 ? __mul24(m.n, m.uu) : m.n * m.uu) - __mul24(m.u, m.u);
@@ -2161,15 +2175,12 @@ __device__ __forceinline__ float subsetBound2D(const Sums2D &m, float invScaleSq
     const float fa = (float)a, fc = (float)c, fb = (float)b;
     const float half = (fa + fc) * 0.5f;
     const float diff = (fa - fc) * 0.5f;
-    // v_sqrt_f32 / v_rcp_f32 are accurate to 1 ulp; the margins below cover that
+    // v_sqrt_f32 is accurate to 1 ulp; the margins below cover that
     const float rad = __builtin_amdgcn_sqrtf(__fmaf_rn(diff, diff, fb * fb));
     const float lam = half * 0.999998f - rad * 1.000002f; // n * scale^2 * (smaller eigenvalue), rounded down
-    const float n = (float)m.n;
-    const float L = lam * invScaleSq;                      // n * R
-    float lb = 0.0f;
-    if (L > n * n * delta * delta)
-        lb = (L * __builtin_amdgcn_rcpf(n) - 2.0f * delta * __builtin_amdgcn_sqrtf(L)) * 0.9999f;
-    return lb > 0.0f ? lb : 0.0f;
+    const float L = fmaxf(lam, 0.0f) * invScaleSq;         // n * R
+    const float lb = (L * rcpN - twoDelta * __builtin_amdgcn_sqrtf(L)) * 0.9999f;
+    return fmaxf(lb, 0.0f);
 }
 
 } // namespace
@@ -2852,7 +2863,13 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                     const float scale = (G8 ? kBoundGrid8 : kBoundGrid16) / (255.0f * __builtin_amdgcn_sqrtf(wsum)); // wave-uniform
                     const float invScaleSq = 1.0f / (scale * scale);
                     // rounding the projected points moves each by at most sqrt(2)/2 grid units
-                    const float delta = (use4 ? A.delta4 : A.delta3) + 0.7072f / scale;
+                    const float twoDelta = 2.0f * ((use4 ? A.delta4 : A.delta3) + 0.7072f / scale);
+                    // formed once per bound set, not per partition (machine LICM is off for this file): the static alpha error
+                    // of the RGB sets, and 1/n of every subset size, lane n of one register (read with ds_bpermute: the
+                    // crossbar, no LDS bytes; every lane is active here, and a lane that were not would read 0 = a smaller bound)
+                    const float staticErr = use4 ? 0.0f : s_static[blk];
+                    const int rcpLane = (int)kRcpDown[lane < 16 ? lane : 16];
+                    auto rcpOf = [&](int n) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(n << 2, rcpLane)); };
                     Proj2D<G8> P;
                     PROF_MARK(2)
                     {
@@ -2910,7 +2927,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                             s0.uu = P.tUU - s1.uu;
                             s0.vv = P.tVV - s1.vv;
                             s0.uv = P.tUV - s1.uv;
-                            lb = subsetBound2D<G8>(s0, invScaleSq, delta) + subsetBound2D<G8>(s1, invScaleSq, delta);
+                            lb = subsetBound2D<G8>(s0, rcpOf(s0.n), invScaleSq, twoDelta) + subsetBound2D<G8>(s1, rcpOf(s1.n), invScaleSq, twoDelta);
                         }
                         else
                         {
@@ -2931,11 +2948,10 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                             s0.uu = P.tUU - s1.uu - s2.uu;
                             s0.vv = P.tVV - s1.vv - s2.vv;
                             s0.uv = P.tUV - s1.uv - s2.uv;
-                            lb = subsetBound2D<G8>(s0, invScaleSq, delta) + subsetBound2D<G8>(s1, invScaleSq, delta) +
-                                 subsetBound2D<G8>(s2, invScaleSq, delta);
+                            lb = subsetBound2D<G8>(s0, rcpOf(s0.n), invScaleSq, twoDelta) + subsetBound2D<G8>(s1, rcpOf(s1.n), invScaleSq, twoDelta) +
+                                 subsetBound2D<G8>(s2, rcpOf(s2.n), invScaleSq, twoDelta);
                         }
-                        if (!use4)
-                            lb += s_static[blk];
+                        lb += staticErr; // (lb >= +0: adding 0.0f changes nothing)
                         lbStore(partition, blk, lb);
                         freshAlive |= (lb > work.err) ? 0u : (1u << k);
                         selA = selA1;

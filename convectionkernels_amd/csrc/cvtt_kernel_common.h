@@ -74,6 +74,23 @@ __device__ __forceinline__ float clampRound(float v, float hi)
     return rintf(fmaxf(fminf(v, hi), 0.0f));
 }
 
+// The index of the LAST refine round of a fast-indexing search, which only v_cvt_pk_u8_f32 consumes (the refiner does not run
+// after it): the upper clamp alone.  v_cvt_pk_u8_f32 converts under the wave's rounding mode -- round-to-nearest-even, the mode
+// every kernel here runs in -- and saturates to 0..255, so for every x <= hi <= 255 it files the byte that
+// (u32)rintf(fmaxf(x, 0.0f)) holds:
+//   * x < 0, -inf included: saturates to 0, what the lower clamp gave;  -0 and (-0.5, 0): round to a zero of either sign, byte 0;
+//   * 0 <= x <= hi: rounding to nearest even IS rintf, and the conversion of the integral value is exact;
+//   * NaN (0 * inf with extreme Options weights) never reaches the conversion: fminf(NaN, hi) = hi, as in clampRound;
+//   * +inf and x > hi: fminf gives hi.
+// tools/cvt_pk_u8_probe.hip checks the identity on all 2^32 bit patterns for hi = 3, 7, 15 on the device.
+__device__ __forceinline__ float clampHigh(float v, float hi) { return fminf(v, hi); }
+
+// 1/n rounded toward zero for the pixel count n of a subset (entry 0, an empty subset: 0), as binary32 bit patterns: L * kRcpDown[n]
+// never exceeds L / n for L >= 0, which is what a lower bound needs (bc7_kernel.hip: subsetBound2D).  One constant per count
+// instead of a v_cvt + v_rcp_f32 (quarter rate, 1 ulp either way) per subset and partition.
+__device__ const u32 kRcpDown[17] = {0x00000000u, 0x3f800000u, 0x3f000000u, 0x3eaaaaaau, 0x3e800000u, 0x3e4cccccu, 0x3e2aaaaau, 0x3e124924u, 0x3e000000u,
+                                     0x3de38e38u, 0x3dccccccu, 0x3dba2e8bu, 0x3daaaaaau, 0x3d9d89d8u, 0x3d924924u, 0x3d888888u, 0x3d800000u};
+
 __device__ __forceinline__ float byteF(u32 pk, int ch) { return (float)((pk >> (8 * ch)) & 0xffu); }
 __device__ __forceinline__ int byteI(u32 pk, int ch) { return (int)((pk >> (8 * ch)) & 0xffu); }
 
