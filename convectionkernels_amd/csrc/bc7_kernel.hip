@@ -18,7 +18,7 @@
 //     partitions they leave alive get the same bound in all channels of each subset (raw integer sums, second tier).
 //   * dual-plane modes 4/5: a block is owned by a lane QUAD, sub-lane = seed point; the block is held channel-major,
 //     the float index selection and refiner sums are the reference's operations, the integer error comes from level
-//     tables + v_perm_b32 + v_dot4_u32_u8 (evalDualFast; evalDual for slow indexing).
+//     tables + v_perm_b32 + v_dot4_u32_u8 (evalDual, bc7_dual.h; slow indexing probes from the same tables).
 //   * single-plane modes 0-3, 6, 7: work pooled over the wave.  Per round the blocks offer their cheapest-bound
 //     partitions, one lane per (item, subset) runs the PCA seed search on LDS-staged pixels, then one lane per CHAIN
 //     (p-bit combination x seed point, with its serial refine rounds: evalChain) evaluates it; an order-preserving
@@ -153,2048 +153,11 @@ extern "C" int cvttmi_bc7_prof_read(unsigned long long *out)
 #define PROF_STAGE_LANES(stage, slot, pred)
 #endif
 
-// Developer-only trial trace (-DCVTT_BC7_DEBUG): per-round results of the dual-plane search of one block.
-#ifdef CVTT_BC7_DEBUG
-__device__ float g_bc7Dbg[2048];
-__device__ unsigned g_bc7DbgBlock = 0xffffffffu;
-extern "C" int cvttmi_bc7_debug_set(unsigned block)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_bc7DbgBlock), &block, sizeof(block)) == hipSuccess ? 0 : -1;
-}
-extern "C" int cvttmi_bc7_debug_read(float *out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bc7Dbg), sizeof(float) * 2048) == hipSuccess ? 0 : -1;
-}
-#endif
-
-namespace
-{
-// ---- BC7 endpoint quantisation (reference BC67.cpp:829-860); all values fit 16 bits ----
-__device__ __forceinline__ int quantizeNoP(int v, int bits) { return ((v << bits) - v + (127 + (1 << (7 - bits)))) >> 8; }
-__device__ __forceinline__ int quantizeP(int v, int bits, int p)
-{
-    const int addend = p ? ((1 << (8 - bits)) - 1) : 255;
-    const int q = ((v << (bits + 1)) - v + addend) >> 9;
-    return (q << 1) | p;
-}
-__device__ __forceinline__ int unquantize(int v, int bits)
-{
-    const int t = v << (8 - bits);
-    return t | (t >> bits);
-}
-
-// Static description of a single-plane mode (BC7 format + reference BC67.cpp:862-938).
-struct ModeDesc
-{
-    int mode;
-    int indexBits;
-    int numP;     // parity combinations: 4 per-endpoint, 2 per-subset, 1 none
-    int quantBits;
-    int unquantBits; // 0 = value is already 8 bit
-};
-
-__device__ __forceinline__ void compressEndpoints(const ModeDesc &md, int (&ep)[2][4], int pIter, bool isRGB)
-{
-    const int nch = isRGB ? 3 : 4;
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-    {
-        // p-bit of endpoint j: per-endpoint modes use bit j of pIter, per-subset modes share
-        // bit 0 (reference BC67.cpp:1307-1309, 872-880)
-        const int p = (md.numP == 4) ? ((pIter >> j) & 1) : (pIter & 1);
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            if (ch < nch)
-            {
-                int v = ep[j][ch];
-                v = (md.numP == 1) ? quantizeNoP(v, md.quantBits) : quantizeP(v, md.quantBits, p);
-                if (md.unquantBits)
-                    v = unquantize(v, md.unquantBits);
-                ep[j][ch] = v;
-            }
-        }
-        if (isRGB)
-            ep[j][3] = 255;
-    }
-}
-
-struct ShapeBest
-{
-    float err;
-    u32 ep0, ep1; // packed RGBA endpoints
-    u32 idxLo, idxHi; // 4 bits per pixel, by pixel position
-};
-
-__device__ __forceinline__ u32 packEP(const int (&e)[4])
-{
-    return (u32)e[0] | ((u32)e[1] << 8) | ((u32)e[2] << 16) | ((u32)e[3] << 24);
-}
-
-// Order-preserving argmin over the 4 lanes of a quad; ties go to the lower sub-lane, which
-// is the earlier candidate in the reference's sequential commit order.
-__device__ __forceinline__ void quadArgminBroadcast(ShapeBest &b, int lane)
-{
-    int who = lane & 3;
-    float err = b.err;
-#pragma unroll
-    for (int step = 1; step <= 2; step <<= 1)
-    {
-        const float oErr = xorLane(err, step);
-        const int oWho = xorLane(who, step);
-        const bool take = (oErr < err) || (oErr == err && oWho < who);
-        err = take ? oErr : err;
-        who = take ? oWho : who;
-    }
-    const int src = (lane & ~3) | who;
-    b.err = err;
-    b.ep0 = __shfl(b.ep0, src);
-    b.ep1 = __shfl(b.ep1, src);
-    b.idxLo = __shfl(b.idxLo, src);
-    b.idxHi = __shfl(b.idxHi, src);
-}
-
-// One CHAIN of a single-plane shape: a (p-bit combination, seed point) pair of the reference's
-// pIter x tweak loops (BC67.cpp:1298-1434) with its refine rounds, run by one lane.  The
-// pixels of the block are read from LDS (`lp`, 16 packed RGBA8 words) in ascending order of
-// the shape's members.  NRC = numRealChannels (3 for modes 0-3).  maxCount = wave-uniform
-// upper bound on popcount(mask).
-// TRACE (BC7_RespectPunchThrough only): every round's error is also written to trialErr[round], and with
-// captureRound >= 0 the result is that round's instead of the best one.
-// `list`: the member pixels in ascending order, 4 bits each (UnitRec::listLo / listHi); best.idxLo / idxHi come back COMPACT: the
-// index of member i in bits [4i, 4i + 4) (expandIndexes puts them at their pixel positions when a block is packed).
-// wantPayload (wave-uniform) = false: only best.err is wanted (probes).
-// A chain cut into pieces (the probes run round 0 of every chain first and the later rounds only once per distinct set of
-// end points): rounds [firstRound, endRound) are run.  firstRound > 0: ep0 / ep1 bring that round's (compressed) end points.
-// endRound < numRefine: ep0 / ep1 take the compressed end points of round endRound away.  r0ep0 / r0ep1: the compressed
-// end points the first executed round used.  (Wave-uniform except for the end points.)
-struct ChainSplit
-{
-    int firstRound, endRound;
-    u32 ep0, ep1;
-    u32 r0ep0, r0ep1;
-};
-
-template <int NRC, bool FAST, bool TRACE>
-__device__ __forceinline__ void evalChain(const u32 *lp, u32 mask, u64 list, int maxCount, const ModeDesc md, const Unfinished &u,
-                                          int pIter, int tweak, bool active, const CvttBc7Args &A,
-                                          const CvttDeviceTables *__restrict__ T, int numRefine, ShapeBest &best,
-                                          const float (&vs)[4], bool wantPayload = true, float *trialErr = nullptr, int captureRound = -1, float *trialErrHbm = nullptr,
-                                          ChainSplit *split = nullptr)
-{
-    const bool isRGB = (NRC == 3);
-    const int range = 1 << md.indexBits;
-    // (literals: the clamp below then needs no canonicalising v_max_f32 per pixel)
-    const float maxValue = md.indexBits == 2 ? 3.0f : md.indexBits == 3 ? 7.0f : 15.0f;
-    const float rcpMaxIndex = T->rcpMaxIndex[md.indexBits];
-    const int weightRcp = (65536 + (range - 1)) / (2 * (range - 1)); // g_weightReciprocals, IndexSelector.cpp:43-62
-    const int count = __popc(mask);
-    const float wRcp = T->rcpTable[count];
-    const float wCount = (float)count;
-    const bool uniformErr = (A.flags & CVTTMI_FLAG_UNIFORM) != 0;
-
-    best.err = FLT_MAX;
-    best.ep0 = best.ep1 = 0;
-    best.idxLo = best.idxHi = 0;
-    const int myCount = active ? count : 0; // member i exists for i < myCount
-    const u32 listLo = (u32)list, listHi = (u32)(list >> 32);
-    // pixel id of member i (i is wave-uniform: the halves of the list are told apart by a scalar branch)
-    auto memberOf = [&](int i) -> int {
-        return (int)(i < 8 ? __builtin_amdgcn_ubfe(listLo, (u32)(4 * i), 4u) : __builtin_amdgcn_ubfe(listHi, (u32)(4 * i - 32), 4u));
-    };
-#ifdef CVTT_BC7_PROFILE
-    u32 profHist[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-#endif
-
-    // static alpha error of RGB modes (reference BC67.cpp:1250-1264); zero on opaque blocks
-    float staticAlphaError = 0.0f;
-    if (isRGB)
-    {
-        u32 acc = 0;
-        for (int i = 0; i < maxCount; i++)
-        {
-            if (i < myCount)
-            {
-                const int d = 255 - byteI(lp[memberOf(i)], 3);
-                acc = (u32)mad24(d, d, (int)acc);
-            }
-        }
-        staticAlphaError = uniformErr ? (float)(int)acc : (float)(int)acc * A.wSq[3];
-    }
-
-    // UnfinishedEndpoints::FinishLDR (reference UnfinishedEndpoints.h:77-91)
-    const float tf0 = T->tweakFactors[md.indexBits - 2][tweak][0];
-    const float tf1 = T->tweakFactors[md.indexBits - 2][tweak][1];
-    int ep[2][4];
-    const int firstRound = split ? split->firstRound : 0, endRound = split ? split->endRound : numRefine;
-    if (firstRound > 0)
-    {
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            ep[0][ch] = byteI(split->ep0, ch);
-            ep[1][ch] = byteI(split->ep1, ch);
-        }
-    }
-    else
-    {
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            if (ch < NRC)
-            {
-                ep[0][ch] = (int)clampRound(u.base[ch] + u.offset[ch] * tf0, 255.0f);
-                ep[1][ch] = (int)clampRound(u.base[ch] + u.offset[ch] * tf1, 255.0f);
-            }
-            else
-                ep[0][ch] = ep[1][ch] = 255;
-        }
-    }
-
-    for (int refine = firstRound; refine < endRound; refine++)
-    {
-        const bool last = (refine == numRefine - 1);
-        if (refine > firstRound || firstRound == 0)
-            compressEndpoints(md, ep, pIter, isRGB);
-        if (split && refine == firstRound)
-        {
-            split->r0ep0 = packEP(ep[0]);
-            split->r0ep1 = packEP(ep[1]);
-        }
-#ifdef CVTT_BC7_PROFILE
-        {
-            const u32 k0 = packEP(ep[0]), k1 = packEP(ep[1]);
-            const int ln = (int)threadIdx.x;
-            bool dupNow = false, dupOld = false;
-            for (int o = 0; o < 4; o++)
-            {
-                const int src = (ln & ~3) | o;
-                const u32 a0 = __shfl(k0, src), a1 = __shfl(k1, src);
-                const bool oAct = __shfl((int)active, src) != 0;
-                if (oAct && o < (ln & 3) && a0 == k0 && a1 == k1) dupNow = true;
-                for (int h = 0; h < refine && h < 4; h++)
-                {
-                    const u32 b0 = __shfl(profHist[h][0], src), b1 = __shfl(profHist[h][1], src);
-                    if (oAct && b0 == k0 && b1 == k1) dupOld = true;
-                }
-            }
-            if (refine < 4) { profHist[refine][0] = k0; profHist[refine][1] = k1; }
-            const u64 mA = __ballot(active), mN = __ballot(active && dupNow), mO = __ballot(active && !dupNow && dupOld);
-            if (ln == 0)
-            {
-                atomicAdd(&g_bc7Dup[0], (unsigned long long)__popcll(mA));
-                atomicAdd(&g_bc7Dup[1], (unsigned long long)__popcll(mN));
-                atomicAdd(&g_bc7Dup[2], (unsigned long long)__popcll(mO));
-                atomicAdd(&g_bc7Dup[3 + (refine < 3 ? refine : 3)], (unsigned long long)__popcll(mN | mO));
-            }
-        }
-#endif
-
-        // IndexSelector<4>::Init (reference IndexSelector.h:27-77)
-        float origin[4], axis[4];
-        int recBase[4], recDelta[4];
-        {
-            float epDW[4];
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-            {
-                origin[ch] = (float)ep[0][ch];
-                epDW[ch] = ((float)ep[1][ch] - origin[ch]) * A.w[ch];
-                // scaled by 4: the reconstructed value (x >> 6) is then byte 1 of the sum
-                recBase[ch] = ((ep[0][ch] << 6) + 32) << 2;
-                recDelta[ch] = (ep[1][ch] - ep[0][ch]) << 2;
-            }
-            float lenSq = epDW[0] * epDW[0];
-#pragma unroll
-            for (int ch = 1; ch < 4; ch++)
-                lenSq = lenSq + epDW[ch] * epDW[ch];
-            lenSq = safeDenom(lenSq);
-            const float mvdls = maxValue / lenSq;
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-                axis[ch] = epDW[ch] * A.w[ch] * mvdls;
-        }
-
-        const v2f org01 = {origin[0], origin[1]}, org23 = {origin[2], origin[3]};
-        const v2f ax01 = {axis[0], axis[1]}, ax23 = {axis[2], axis[3]};
-        const v2f w01 = {A.w[0], A.w[1]}, w23 = {A.w[2], A.w[3]};
-        u32 err[4] = {0, 0, 0, 0};
-        float slowErr = 0.0f;
-        v2f tv01 = {0.0f, 0.0f}, tv23 = {0.0f, 0.0f};
-        float tt = 0.0f, ts = 0.0f;
-        u32 idxLo = 0, idxHi = 0; // compact: member i in bits [4i, 4i + 4)
-
-        for (int i = 0; i < maxCount; i++)
-        {
-            if (i < myCount)
-            {
-                const u32 pk = lp[memberOf(i)];
-                // SelectIndexLDR (reference IndexSelector.h:124-131)
-                const v2f x01 = {byteF(pk, 0), byteF(pk, 1)}, x23 = {byteF(pk, 2), byteF(pk, 3)};
-                const v2f p01 = (x01 - org01) * ax01, p23 = (x23 - org23) * ax23;
-                float dist = p01.x + p01.y;
-                dist = dist + p23.x;
-                dist = dist + p23.y;
-                float fidx = clampRound(dist, maxValue);
-                int index = (int)fidx;
-
-                if (FAST)
-                {
-                    // ReconstructLDR_BC7 + ComputeErrorLDR (IndexSelector.h:90-100, BCCommon.h:24-29)
-                    const int wgt = mad24(weightRcp, index, 256) >> 9;
-                    err[0] = accumulateChannelError<0>(wgt, recDelta[0], recBase[0], pk, err[0]);
-                    err[1] = accumulateChannelError<1>(wgt, recDelta[1], recBase[1], pk, err[1]);
-                    err[2] = accumulateChannelError<2>(wgt, recDelta[2], recBase[2], pk, err[2]);
-                    if (NRC == 4)
-                        err[3] = accumulateChannelError<3>(wgt, recDelta[3], recBase[3], pk, err[3]);
-                }
-                else
-                {
-                    // slow indexing: also probe index-1 / index+1 (reference BC67.cpp:1367-1386)
-                    float bestE = 0.0f;
-                    const int index0 = index;
-#pragma unroll
-                    for (int probe = 0; probe < 3; probe++)
-                    {
-                        int cand = index0;
-                        if (probe == 1) cand = (index0 > 1 ? index0 : 1) - 1;
-                        if (probe == 2) cand = (index0 + 1 < range - 1) ? index0 + 1 : range - 1;
-                        const int wgt = mad24(weightRcp, cand, 256) >> 9;
-                        // the reconstructed channel is byte 1 of w * delta4 + base4; its difference to the pixel and the
-                        // square are taken as floats (exact on these integers, see evalDual: plain f32 instructions)
-                        const float xs[4] = {x01.x, x01.y, x23.x, x23.y};
-                        float e4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                        for (int ch = 0; ch < NRC; ch++)
-                        {
-                            const float d = byteF((u32)madI24(wgt, recDelta[ch], recBase[ch]), 1) - xs[ch];
-                            e4[ch] = d * d;
-                        }
-                        float e;
-                        if (uniformErr)
-                            e = ((e4[0] + e4[1]) + e4[2]) + e4[3];
-                        else
-                        {
-                            e = e4[0] * A.wSq[0];
-                            e = e + e4[1] * A.wSq[1];
-                            e = e + e4[2] * A.wSq[2];
-                            e = e + e4[3] * A.wSq[3];
-                        }
-                        if (probe == 0)
-                            bestE = e;
-                        else
-                        {
-                            // both alternatives derive from the initial index (BC67.cpp:1367-1386); the winner is tracked as an
-                            // integer and converted once, and the comparison that moves it also serves the minimum
-                            const bool better = e < bestE;
-                            bestE = better ? e : bestE;
-                            index = better ? cand : index;
-                        }
-                    }
-                    slowErr = slowErr + bestE;
-                    fidx = (float)index;
-                }
-
-                if (!last)
-                {
-                    // EndpointRefiner::ContributeUnweightedPW (EndpointRefiner.h:78-92)
-                    const float t = fidx * rcpMaxIndex;
-                    const v2f t2 = {t, t};
-                    const v2f v01 = x01 * w01, v23 = x23 * w23; // channel 3 is unused when NRC == 3
-                    tv01 = tv01 + t2 * v01;
-                    tv23 = tv23 + t2 * v23;
-                    tt = tt + t * t;
-                    ts = ts + t;
-                }
-                if (wantPayload)
-                {
-                    if (i < 8)
-                        idxLo |= (u32)index << (4 * i);
-                    else
-                        idxHi |= (u32)index << (4 * i - 32);
-                }
-            }
-        }
-
-        // AggregatedError<4>::Finalize (reference AggregatedError.h:29-46)
-        float shapeError;
-        if (FAST)
-        {
-            if (uniformErr)
-                shapeError = (float)(int)(err[0] + err[1] + err[2] + err[3]);
-            else
-            {
-                shapeError = (float)(int)err[0] * A.wSq[0];
-                shapeError = shapeError + (float)(int)err[1] * A.wSq[1];
-                shapeError = shapeError + (float)(int)err[2] * A.wSq[2];
-                shapeError = shapeError + (float)(int)err[3] * A.wSq[3];
-            }
-        }
-        else
-            shapeError = slowErr;
-        if (isRGB)
-            shapeError = shapeError + staticAlphaError;
-
-        if (TRACE && active)
-        {
-            // (two pointers, not one: the LDS stores stay ds_write instead of turning into flat stores)
-            if (trialErrHbm)
-                trialErrHbm[refine] = shapeError;
-            else if (trialErr)
-                trialErr[refine] = shapeError;
-        }
-        const bool take = (TRACE && captureRound >= 0) ? (refine == captureRound) : (shapeError < best.err);
-        if (active && take)
-        {
-            best.err = shapeError;
-            best.ep0 = packEP(ep[0]);
-            best.ep1 = packEP(ep[1]);
-            best.idxLo = idxLo;
-            best.idxHi = idxHi;
-        }
-
-        if (!last)
-        {
-            // EndpointRefiner::GetRefinedEndpointsLDR (EndpointRefiner.h:99-152)
-            const float tv[4] = {tv01.x, tv01.y, tv23.x, tv23.y};
-            float adenom = (tt * wCount - ts * ts) * wRcp;
-            const bool adenomZero = (adenom == 0.0f);
-            if (adenomZero)
-                adenom = 1.0f;
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-            {
-                if (ch < NRC)
-                {
-                    const float a = (tv[ch] - ts * vs[ch] * wRcp) / adenom;
-                    const float b = (vs[ch] - a * ts) * wRcp;
-                    float p1 = b;
-                    float p2 = a + b;
-                    if (adenomZero)
-                    {
-                        p1 = vs[ch] * wRcp;
-                        p2 = p1;
-                    }
-                    ep[0][ch] = (int)clampRound(p1 * A.rcpW[ch], 255.0f);
-                    ep[1][ch] = (int)clampRound(p2 * A.rcpW[ch], 255.0f);
-                }
-                else
-                    ep[0][ch] = ep[1][ch] = 0; // overwritten with 255 by compressEndpoints
-            }
-        }
-    }
-    if (split && endRound < numRefine)
-    {
-        compressEndpoints(md, ep, pIter, isRGB);
-        split->ep0 = packEP(ep[0]);
-        split->ep1 = packEP(ep[1]);
-    }
-}
-
-// Order-preserving argmin over aligned groups of `width` lanes (4, 8 or 16): ties go to the
-// lower lane, i.e. the earlier chain in the reference's sequential commit order.
-__device__ __forceinline__ void groupArgminBroadcast(ShapeBest &b, int lane, int width)
-{
-    int who = lane;
-    float err = b.err;
-    // (width is 4, 8 or 16, wave-uniform: the steps are spelled out so that each is a ds_swizzle with a literal pattern)
-#define CVTT_GROUP_STEP(STEP)                                             \
-    {                                                                     \
-        const float oErr = xorLane(err, STEP);                            \
-        const int oWho = xorLane(who, STEP);                              \
-        const bool take = (oErr < err) || (oErr == err && oWho < who);    \
-        err = take ? oErr : err;                                          \
-        who = take ? oWho : who;                                          \
-    }
-    CVTT_GROUP_STEP(1)
-    CVTT_GROUP_STEP(2)
-    if (width > 4)
-        CVTT_GROUP_STEP(4)
-    if (width > 8)
-        CVTT_GROUP_STEP(8)
-#undef CVTT_GROUP_STEP
-    b.err = err;
-    b.ep0 = __shfl(b.ep0, who);
-    b.ep1 = __shfl(b.ep1, who);
-    b.idxLo = __shfl(b.idxLo, who);
-    b.idxHi = __shfl(b.idxHi, who);
-}
-
-// Pixel source for the PCA passes of a block staged in LDS.
-struct FetchLDS
-{
-    const u32 *lp;
-    const float (&w)[4];
-    template <int N>
-    __device__ __forceinline__ void get(int px, float (&v)[N]) const
-    {
-        const u32 pk = lp[px];
-#pragma unroll
-        for (int ch = 0; ch < N; ch++)
-            v[ch] = byteF(pk, ch) * w[ch];
-    }
-};
-
-template <int N>
-__device__ __forceinline__ void pcaEndpointsLDS(const u32 *lp, u32 mask, const float (&w)[4], Unfinished &u, float *sums)
-{
-    const FetchLDS F = {lp, w};
-    Moments<N> m;
-    pcaMomentsT<N>(F, mask, m, sums);
-    pcaFinishT<N>(F, mask, w, m, u);
-}
-
-// What one lane of the PCA pass leaves for the chain lanes of its (block, partition, subset).
-struct UnitRec
-{
-    float base[4];
-    float offset[4];
-    u32 packed;  // mask | numTweak << 16 | blk << 20 | slot << 24  (slot = item * subsets + subset: where the subset's result goes)
-    float scErr; // BC7_TrySingleColor: error of the fixed candidate (FLT_MAX when not tried)
-    // the refiner's m_v of the subset: sum of the pre-weighted member pixels in ascending order (EndpointRefiner.h:78-92).
-    // It does not depend on the indexes, so the seed lane takes it once for all chains and rounds of the unit.
-    float vs[4];
-    // the member pixels of the subset in ascending order, 4 bits each: the chain lanes read pixel i of their subset with one
-    // bit-field extract at a wave-uniform position instead of popping a per-lane bit mask
-    u32 listLo, listHi;
-    __device__ __forceinline__ u32 mask() const { return packed & 0xffffu; }
-    __device__ __forceinline__ int numTweak() const { return (int)((packed >> 16) & 7u); }
-    __device__ __forceinline__ int blk() const { return (int)((packed >> 20) & 15u); }
-    __device__ __forceinline__ int slot() const { return (int)(packed >> 24); }
-};
-
-struct WorkState
-{
-    float err;
-    int mode;
-    int partOrIS; // partition, or index selector for modes 4/5 (union in the reference, BC67.cpp:67-75)
-    int rotation;
-    u32 ep[3][2];
-    u32 idxLo, idxHi;   // primary indexes, 4 bits per pixel
-    u32 idx2Lo, idx2Hi; // secondary indexes (modes 4/5)
-};
-
-// Fix-ups + bit packing of a mode 4 / mode 5 block (reference BC67.cpp:2003-2203) by one lane: with the mode a template
-// parameter every field sits at a constant bit position, so the 66 fields cost a shift-or each instead of the generic
-// packer's per-lane field arithmetic (the kernel keeps that one for the other modes).
-template <int MODE>
-__device__ __forceinline__ void packDualPlane(const WorkState &work, u32 &w0, u32 &w1, u32 &w2, u32 &w3)
-{
-    constexpr int rgbBits = (MODE == 4) ? 5 : 7, alphaBits = (MODE == 4) ? 6 : 8, alphaIndexBits = (MODE == 4) ? 3 : 2;
-    constexpr u32 idxOnes = 0x33333333u, idx2Ones = (MODE == 4) ? 0x77777777u : 0x33333333u;
-    u32 iLo = work.idxLo, iHi = work.idxHi, jLo = work.idx2Lo, jHi = work.idx2Hi;
-    // the anchor (pixel 0) of either index set must have its top bit clear: complement the set and exchange the
-    // endpoints it interpolates (every 4-bit slot holds at most the set's maximum, so the complement is an XOR)
-    bool flipRGB = ((iLo >> 1) & 1u) != 0;
-    bool flipAlpha = ((jLo >> (alphaIndexBits - 1)) & 1u) != 0;
-    if (flipRGB)
-    {
-        iLo ^= idxOnes;
-        iHi ^= idxOnes;
-    }
-    if (flipAlpha)
-    {
-        jLo ^= idx2Ones;
-        jHi ^= idx2Ones;
-    }
-    const int indexSelector = (MODE == 4) ? work.partOrIS : 0;
-    if (indexSelector)
-    {
-        const bool t = flipRGB;
-        flipRGB = flipAlpha;
-        flipAlpha = t;
-    }
-    u32 e0 = work.ep[0][0], e1 = work.ep[0][1];
-    if (flipRGB)
-    {
-        const u32 a = e0, b = e1;
-        e0 = (a & 0xff000000u) | (b & 0x00ffffffu);
-        e1 = (b & 0xff000000u) | (a & 0x00ffffffu);
-    }
-    if (flipAlpha)
-    {
-        const u32 a = e0, b = e1;
-        e0 = (a & 0x00ffffffu) | (b & 0xff000000u);
-        e1 = (b & 0x00ffffffu) | (a & 0xff000000u);
-    }
-    u64 lo = 0, hi = 0;
-    auto put = [&](u32 value, int off) {
-        const u64 v = (u64)value;
-        if (off < 64)
-        {
-            lo |= v << off;
-            if (off > 56)
-                hi |= v >> (64 - off); // fields are at most 8 bits wide
-        }
-        else
-            hi |= v << (off - 64);
-    };
-    put(1u << MODE, 0);
-    put((u32)work.rotation, MODE + 1);
-    if (MODE == 4)
-        put((u32)indexSelector, 7);
-    constexpr int epBase = 8;
-#pragma unroll
-    for (int g = 0; g < 6; g++)
-    {
-        const u32 e = (g & 1) ? e1 : e0;
-        put(((e >> (8 * (g >> 1))) & 0xffu) >> (8 - rgbBits), epBase + g * rgbBits);
-    }
-    constexpr int alphaBase = epBase + 6 * rgbBits;
-    put((e0 >> 24) >> (8 - alphaBits), alphaBase);
-    put((e1 >> 24) >> (8 - alphaBits), alphaBase + alphaBits);
-    constexpr int idxBase = alphaBase + 2 * alphaBits;
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-        put(((px < 8 ? iLo : iHi) >> (4 * (px & 7))) & 0xfu, idxBase + 2 * px - (px > 0 ? 1 : 0));
-    constexpr int idx2Base = idxBase + 31;
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-        put(((px < 8 ? jLo : jHi) >> (4 * (px & 7))) & 0xfu, idx2Base + alphaIndexBits * px - (px > 0 ? 1 : 0));
-    w0 = (u32)lo;
-    w1 = (u32)(lo >> 32);
-    w2 = (u32)hi;
-    w3 = (u32)(hi >> 32);
-}
-
-// In-place channel rotation of the packed pixels: rotation r > 0 exchanges channel r-1 with
-// alpha (reference BC67.cpp:1695-1698).  The exchange is an involution.
-__device__ __forceinline__ u32 rotatePixel(u32 pk, int rotation)
-{
-    if (rotation == 1) return (pk & 0x00ffff00u) | (pk >> 24) | (pk << 24);
-    if (rotation == 2) return (pk & 0x00ff00ffu) | ((pk >> 16) & 0x0000ff00u) | ((pk << 16) & 0xff000000u);
-    if (rotation == 3) return (pk & 0x0000ffffu) | ((pk >> 8) & 0x00ff0000u) | ((pk << 8) & 0xff000000u);
-    return pk;
-}
-
-__device__ __forceinline__ void levelTable(int e0, int e1, bool threeBit, u32 &tabLo, u32 &tabHi);
-
-struct DualInv
-{
-    const u32 *words; // s_raw + block index
-    int rowSq[4], rowVs[4];
-    u32 minMax;
-};
-
-// One (mode, rotation, index selector) configuration of the dual-plane modes 4/5
-// (reference BC67.cpp:1725-1940): sub-lane c runs seed point c.  `pix` is already rotated so
-// that byte 3 is the separately coded channel; w/wSq/rcpW are rotated the same way.
-template <bool FAST>
-// `sP`: the block's 16 pixels in LDS, already rotated (byte 3 = the separately coded channel), read four at a time in every
-// round instead of living in 16 registers; `minMax` = min | max << 8 of the separately coded channel.
-__device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int mode, int indexSelector, const Unfinished &uRGB,
-                                         int numTweak, const float (&rw)[4], const float (&rwSq)[4],
-                                         const float (&rrcpW)[4], u32 flags, const CvttDeviceTables *__restrict__ T,
-                                         int numRefine, int lane, ShapeBest &bestRGB, ShapeBest &bestA)
-{
-    const int c = lane & 3;
-    int rgbPrec, alphaPrec;
-    if (mode == 4)
-    {
-        rgbPrec = indexSelector ? 3 : 2;
-        alphaPrec = indexSelector ? 2 : 3;
-    }
-    else
-        rgbPrec = alphaPrec = 2;
-    const int rgbRange = 1 << rgbPrec, alphaRange = 1 << alphaPrec;
-    const float rgbMax = (float)(rgbRange - 1), alphaMaxV = (float)(alphaRange - 1);
-    const int rgbWR = (65536 + (rgbRange - 1)) / (2 * (rgbRange - 1));
-    const int alphaWR = (65536 + (alphaRange - 1)) / (2 * (alphaRange - 1));
-    const float rgbRcpMax = T->rcpMaxIndex[rgbPrec], alphaRcpMax = T->rcpMaxIndex[alphaPrec];
-    const float wRcp16 = T->rcpTable[16];
-    const bool uniformErr = (flags & CVTTMI_FLAG_UNIFORM) != 0;
-
-    bestRGB.err = bestA.err = FLT_MAX;
-    bestRGB.ep0 = bestRGB.ep1 = bestRGB.idxLo = bestRGB.idxHi = 0;
-    bestA.ep0 = bestA.ep1 = bestA.idxLo = bestA.idxHi = 0;
-
-    const u32 minMax = inv.minMax;
-    const int alphaMin = (int)(minMax & 0xffu), alphaMax = (int)(minMax >> 8);
-
-    const int tweak = c;
-    if (tweak < numTweak)
-    {
-        int ep[2][4];
-        {
-            const float tf0 = T->tweakFactors[rgbPrec - 2][tweak][0];
-            const float tf1 = T->tweakFactors[rgbPrec - 2][tweak][1];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-            {
-                ep[0][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf0, 255.0f);
-                ep[1][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf1, 255.0f);
-            }
-            // TweakAlpha (reference BC67.cpp:815-827)
-            const float af0 = T->tweakFactors[alphaPrec - 2][tweak][0];
-            const float af1 = T->tweakFactors[alphaPrec - 2][tweak][1];
-            const float base = (float)alphaMin;
-            const float offs = (float)alphaMax - base;
-            ep[0][3] = (int)clampRound(base + offs * af0, 255.0f);
-            ep[1][3] = (int)clampRound(base + offs * af1, 255.0f);
-        }
-
-        for (int refine = 0; refine < numRefine; refine++)
-        {
-            const bool last = (refine == numRefine - 1);
-            // CompressEndpoints4 / 5 (reference BC67.cpp:901-923)
-            const int cb = (mode == 4) ? 5 : 7;
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-            {
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    ep[j][ch] = unquantize(quantizeNoP(ep[j][ch], cb), cb);
-                if (mode == 4)
-                    ep[j][3] = unquantize(quantizeNoP(ep[j][3], 6), 6);
-            }
-
-            // IndexSelector<3> (rotated weights) and IndexSelector<1> (weight 1.0)
-            float origin[4], axis[4];
-            int recBase[4], recDelta[4];
-            {
-                float epDW[3];
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                {
-                    origin[ch] = (float)ep[0][ch];
-                    epDW[ch] = ((float)ep[1][ch] - origin[ch]) * rw[ch];
-                }
-                float lenSq = epDW[0] * epDW[0];
-                lenSq = lenSq + epDW[1] * epDW[1];
-                lenSq = lenSq + epDW[2] * epDW[2];
-                lenSq = safeDenom(lenSq);
-                const float mvdls = rgbMax / lenSq;
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    axis[ch] = epDW[ch] * rw[ch] * mvdls;
-                origin[3] = (float)ep[0][3];
-                const float aDW = (float)ep[1][3] - origin[3];
-                const float aLen = safeDenom(aDW * aDW);
-                axis[3] = aDW * (alphaMaxV / aLen);
-#pragma unroll
-                for (int ch = 0; ch < 4; ch++)
-                {
-                    // scaled by 4: the reconstructed value (x >> 6) is then byte 1 of the sum
-                    recBase[ch] = ((ep[0][ch] << 6) + 32) << 2;
-                    recDelta[ch] = (ep[1][ch] - ep[0][ch]) << 2;
-                }
-            }
-            const v2f org01 = {origin[0], origin[1]}, org23 = {origin[2], origin[3]};
-            const v2f ax01 = {axis[0], axis[1]}, ax23 = {axis[2], axis[3]};
-            const v2f w01 = {rw[0], rw[1]}, w23 = {rw[2], 1.0f};
-            const v2f rcpMax2 = {rgbRcpMax, alphaRcpMax};
-            // slow indexing: the 4 / 8 values an index can reconstruct, per channel, as bytes (the fast path's level tables):
-            // the three candidates of a pixel are then one v_perm_b32 per channel instead of a weight and a multiply-add each
-            u32 tLo[4] = {0, 0, 0, 0}, tHi[4] = {0, 0, 0, 0};
-            if (!FAST)
-            {
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    levelTable(ep[0][ch], ep[1][ch], rgbPrec == 3, tLo[ch], tHi[ch]);
-                levelTable(ep[0][3], ep[1][3], alphaPrec == 3, tLo[3], tHi[3]);
-            }
-
-            u32 err[4] = {0, 0, 0, 0};
-            float slowRGB = 0.0f, slowA = 0.0f;
-            v2f tv01 = {0.0f, 0.0f}, tv23 = {0.0f, 0.0f};
-            v2f tt2 = {0.0f, 0.0f}, ts2 = {0.0f, 0.0f}; // {RGB plane, alpha plane}
-            u32 rgbLo = 0, rgbHi = 0, aLo = 0, aHi = 0;
-
-            const u32 *sPr = sP; // opaque to the optimiser: the loads stay inside the round (see evalDualFast)
-            asm volatile("" : "+v"(sPr));
-            // four pixels per trip, the trips not unrolled: unrolled sixteen times, the three probes of every pixel kept so
-            // much in flight that this instantiation could not be held in the 128 registers of four waves per SIMD
-#pragma unroll 1
-            for (int g = 0; g < 4; g++)
-            {
-            const uint4 L = *reinterpret_cast<const uint4 *>(sPr + 4 * g);
-            u32 r4 = 0, a4 = 0; // the group's indexes, 4 bits per pixel
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-            {
-                const u32 pk = k == 0 ? L.x : k == 1 ? L.y : k == 2 ? L.z : L.w;
-                const v2f x01 = {byteF(pk, 0), byteF(pk, 1)}, x23 = {byteF(pk, 2), byteF(pk, 3)};
-                const v2f p01 = (x01 - org01) * ax01, p23 = (x23 - org23) * ax23;
-                float dist = p01.x + p01.y;
-                dist = dist + p23.x;
-                float fRGB = clampRound(dist, rgbMax);
-                float fA = clampRound(p23.y, alphaMaxV);
-                int iRGB = (int)fRGB, iA = (int)fA;
-
-                if (FAST)
-                {
-                    const int wgt = mad24(rgbWR, iRGB, 256) >> 9;
-                    err[0] = accumulateChannelError<0>(wgt, recDelta[0], recBase[0], pk, err[0]);
-                    err[1] = accumulateChannelError<1>(wgt, recDelta[1], recBase[1], pk, err[1]);
-                    err[2] = accumulateChannelError<2>(wgt, recDelta[2], recBase[2], pk, err[2]);
-                    const int wa = mad24(alphaWR, iA, 256) >> 9;
-                    err[3] = accumulateChannelError<3>(wa, recDelta[3], recBase[3], pk, err[3]);
-                }
-                else
-                {
-                    // reference BC67.cpp:1834-1880
-                    float eRGB = 0.0f, eA = 0.0f;
-                    const int c1R = (iRGB > 1 ? iRGB : 1) - 1, c2R = (iRGB + 1 < rgbRange - 1) ? iRGB + 1 : rgbRange - 1;
-                    const int c1A = (iA > 1 ? iA : 1) - 1, c2A = (iA + 1 < alphaRange - 1) ? iA + 1 : alphaRange - 1;
-                    const u32 selR = (u32)iRGB | ((u32)c1R << 8) | ((u32)c2R << 16) | 0x0c000000u;
-                    const u32 selA = (u32)iA | ((u32)c1A << 8) | ((u32)c2A << 16) | 0x0c000000u;
-                    // byte k = the value candidate k reconstructs
-                    const u32 rec0 = __builtin_amdgcn_perm(tHi[0], tLo[0], selR), rec1 = __builtin_amdgcn_perm(tHi[1], tLo[1], selR),
-                              rec2 = __builtin_amdgcn_perm(tHi[2], tLo[2], selR), rec3 = __builtin_amdgcn_perm(tHi[3], tLo[3], selA);
-                    auto probeOne = [&](auto kTag, int candRGB, int candA) {
-                        constexpr int K = decltype(kTag)::value;
-                        // (rec - px)^2 as floats: byte -> float conversions, a subtract and a multiply are exact on these
-                        // integers (|d| <= 255, d^2 < 2^24), so the squares are the numbers the integer form converts -- and
-                        // they are plain f32 instructions, which a second wave can issue alongside (SDWA and 24-bit
-                        // multiplies cannot)
-                        const float d0 = byteF(rec0, K) - x01.x, d1 = byteF(rec1, K) - x01.y, d2 = byteF(rec2, K) - x23.x, d3 = byteF(rec3, K) - x23.y;
-                        const float e3[3] = {d0 * d0, d1 * d1, d2 * d2};
-                        const float e1 = d3 * d3;
-                        float er, ea;
-                        if (uniformErr)
-                        {
-                            er = (e3[0] + e3[1]) + e3[2];
-                            ea = e1;
-                        }
-                        else
-                        {
-                            er = e3[0] * rwSq[0];
-                            er = er + e3[1] * rwSq[1];
-                            er = er + e3[2] * rwSq[2];
-                            ea = e1 * rwSq[3];
-                        }
-                        if (K == 0)
-                        {
-                            eRGB = er;
-                            eA = ea;
-                        }
-                        else
-                        {
-                            // (the winner is tracked as an integer and converted once; equal errors are equal bits, so the
-                            // comparison that moves the index also serves the minimum)
-                            const bool bR = er < eRGB, bA = ea < eA;
-                            eRGB = bR ? er : eRGB;
-                            eA = bA ? ea : eA;
-                            iRGB = bR ? candRGB : iRGB;
-                            iA = bA ? candA : iA;
-                        }
-                    };
-                    probeOne(std::integral_constant<int, 0>{}, iRGB, iA);
-                    probeOne(std::integral_constant<int, 1>{}, c1R, c1A);
-                    probeOne(std::integral_constant<int, 2>{}, c2R, c2A);
-                    fRGB = (float)iRGB;
-                    fA = (float)iA;
-                    slowRGB = slowRGB + eRGB;
-                    slowA = slowA + eA;
-                }
-
-                if (!last)
-                {
-                    // EndpointRefiner<3> with the rotated weights and EndpointRefiner<1> with weight 1
-                    const v2f f2 = {fRGB, fA};
-                    const v2f t2 = f2 * rcpMax2;
-                    const v2f tt = {t2.x, t2.x};
-                    const v2f v01 = x01 * w01, v23 = x23 * w23;
-                    tv01 = tv01 + tt * v01;
-                    tv23 = tv23 + t2 * v23;
-                    tt2 = tt2 + t2 * t2;
-                    ts2 = ts2 + t2;
-                }
-                r4 |= (u32)iRGB << (4 * k);
-                a4 |= (u32)iA << (4 * k);
-            }
-            if (g < 2)
-            {
-                rgbLo |= r4 << (16 * g);
-                aLo |= a4 << (16 * g);
-            }
-            else
-            {
-                rgbHi |= r4 << (16 * (g - 2));
-                aHi |= a4 << (16 * (g - 2));
-            }
-            }
-
-            float errorRGB, errorA;
-            if (FAST)
-            {
-                if (uniformErr)
-                {
-                    errorRGB = (float)(int)(err[0] + err[1] + err[2]);
-                    errorA = (float)(int)err[3];
-                }
-                else
-                {
-                    errorRGB = (float)(int)err[0] * rwSq[0];
-                    errorRGB = errorRGB + (float)(int)err[1] * rwSq[1];
-                    errorRGB = errorRGB + (float)(int)err[2] * rwSq[2];
-                    errorA = (float)(int)err[3] * rwSq[3];
-                }
-            }
-            else
-            {
-                errorRGB = slowRGB;
-                errorA = slowA;
-            }
-
-#ifdef CVTT_BC7_DEBUG
-            if (blockIdx.x * 16u + (u32)(lane >> 2) == g_bc7DbgBlock)
-            {
-                // slot: ((mode-4)*8 + rotationHint*2 + indexSelector) is not known here; the caller's config order is
-                // recovered from the write counter kept in element 0
-                const int cfgSlot = (int)g_bc7Dbg[0];
-                float *d = &g_bc7Dbg[16 + ((cfgSlot * 4 + c) * 3 + refine) * 12];
-                d[0] = (float)mode; d[1] = (float)indexSelector; d[2] = (float)c; d[3] = (float)refine;
-                d[4] = errorRGB; d[5] = errorA;
-                d[6] = (float)ep[0][0]; d[7] = (float)ep[0][1]; d[8] = (float)ep[0][2];
-                d[9] = (float)ep[1][0]; d[10] = (float)ep[1][1]; d[11] = (float)ep[1][2];
-            }
-#endif
-            if (errorRGB < bestRGB.err)
-            {
-                bestRGB.err = errorRGB;
-                bestRGB.ep0 = (u32)ep[0][0] | ((u32)ep[0][1] << 8) | ((u32)ep[0][2] << 16);
-                bestRGB.ep1 = (u32)ep[1][0] | ((u32)ep[1][1] << 8) | ((u32)ep[1][2] << 16);
-                bestRGB.idxLo = rgbLo;
-                bestRGB.idxHi = rgbHi;
-            }
-            if (errorA < bestA.err)
-            {
-                bestA.err = errorA;
-                bestA.ep0 = (u32)ep[0][3] << 24;
-                bestA.ep1 = (u32)ep[1][3] << 24;
-                bestA.idxLo = aLo;
-                bestA.idxHi = aHi;
-            }
-
-            if (!last)
-            {
-                // EndpointRefiner<3> / <1>::GetRefinedEndpointsLDR, 16 contributions each
-                // (the sums of the pre-weighted pixels do not depend on the indexes: taken once per block, see evalDualFast)
-                const float vs[4] = {__builtin_bit_cast(float, inv.words[inv.rowVs[0]]), __builtin_bit_cast(float, inv.words[inv.rowVs[1]]),
-                                     __builtin_bit_cast(float, inv.words[inv.rowVs[2]]), __builtin_bit_cast(float, inv.words[inv.rowVs[3]])};
-                {
-                    const float tv[4] = {tv01.x, tv01.y, tv23.x, tv23.y};
-                    const float ttRGB = tt2.x, tsRGB = ts2.x;
-                    float adenom = (ttRGB * 16.0f - tsRGB * tsRGB) * wRcp16;
-                    const bool z = (adenom == 0.0f);
-                    if (z) adenom = 1.0f;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ch++)
-                    {
-                        const float a = (tv[ch] - tsRGB * vs[ch] * wRcp16) / adenom;
-                        const float b = (vs[ch] - a * tsRGB) * wRcp16;
-                        float p1 = b, p2 = a + b;
-                        if (z)
-                        {
-                            p1 = vs[ch] * wRcp16;
-                            p2 = p1;
-                        }
-                        ep[0][ch] = (int)clampRound(p1 * rrcpW[ch], 255.0f);
-                        ep[1][ch] = (int)clampRound(p2 * rrcpW[ch], 255.0f);
-                    }
-                }
-                {
-                    const float tv[4] = {tv01.x, tv01.y, tv23.x, tv23.y};
-                    const float ttA = tt2.y, tsA = ts2.y;
-                    float adenom = (ttA * 16.0f - tsA * tsA) * wRcp16;
-                    const bool z = (adenom == 0.0f);
-                    if (z) adenom = 1.0f;
-                    const float a = (tv[3] - tsA * vs[3] * wRcp16) / adenom;
-                    const float b = (vs[3] - a * tsA) * wRcp16;
-                    float p1 = b, p2 = a + b;
-                    if (z)
-                    {
-                        p1 = vs[3] * wRcp16;
-                        p2 = p1;
-                    }
-                    ep[0][3] = (int)clampRound(p1, 255.0f);
-                    ep[1][3] = (int)clampRound(p2, 255.0f);
-                }
-            }
-        }
-    }
-    quadArgminBroadcast(bestRGB, lane);
-    quadArgminBroadcast(bestA, lane);
-}
-
-
-typedef unsigned short v2us __attribute__((ext_vector_type(2)));
-
-// The 4 or 8 reconstructed values of one channel, ((64 - w) * e0 + w * e1 + 32) >> 6 for the BC7 weights w of a 2- or
-// 3-bit index (reference IndexSelector.h:90-100), as bytes: tabLo = levels 0..3, tabHi = levels 4..7 (3-bit only).
-// Two levels per instruction in packed 16-bit lanes (every intermediate fits 16 bits).
-__device__ __forceinline__ void levelTable(int e0, int e1, bool threeBit, u32 &tabLo, u32 &tabHi)
-{
-    const u32 base = (u32)((e0 << 6) + 32), delta = (u32)(e1 - e0) & 0xffffu;
-    const v2us BB = __builtin_bit_cast(v2us, base | (base << 16)), DD = __builtin_bit_cast(v2us, delta | (delta << 16));
-    const v2us six = {6, 6};
-    // weight pairs: 2-bit {0, 21}, {43, 64}; 3-bit {0, 9}, {18, 27}, {37, 46}, {55, 64}
-    const u32 w01 = threeBit ? (0u | (9u << 16)) : (0u | (21u << 16));
-    const u32 w23 = threeBit ? (18u | (27u << 16)) : (43u | (64u << 16));
-    const v2us r01 = (__builtin_bit_cast(v2us, w01) * DD + BB) >> six;
-    const v2us r23 = (__builtin_bit_cast(v2us, w23) * DD + BB) >> six;
-    tabLo = __builtin_amdgcn_perm(__builtin_bit_cast(u32, r23), __builtin_bit_cast(u32, r01), 0x06040200u);
-    tabHi = 0;
-    if (threeBit)
-    {
-        const v2us r45 = (__builtin_bit_cast(v2us, 37u | (46u << 16)) * DD + BB) >> six;
-        const v2us r67 = (__builtin_bit_cast(v2us, 55u | (64u << 16)) * DD + BB) >> six;
-        tabHi = __builtin_amdgcn_perm(__builtin_bit_cast(u32, r67), __builtin_bit_cast(u32, r45), 0x06040200u);
-    }
-}
-
-// four byte-wide indexes -> four nibbles in the low 16 bits
-__device__ __forceinline__ u32 nibblesOf(u32 b4)
-{
-    const u32 t = b4 | (b4 >> 4);
-    return __builtin_amdgcn_perm(0u, t, 0x0c0c0200u);
-}
-
-// evalDual for fast indexing, on channel-major pixels: P[ch][g] holds channel ch of pixels 4g..4g+3 (one byte each),
-// channels already in rotated order (P[3] = the separately coded channel).  The float index selection and the refiner
-// are the reference's operation for operation; the integer error sum(rec - px)^2 is evaluated per channel as
-// sum(rec^2) - 2 sum(rec * px) + sum(px^2) with the reconstructed bytes looked up by v_perm_b32 from the level table
-// and the sums taken by v_dot4_u32_u8 over four pixels at a time -- integers, so the result is the same number.
-// Invariants of the block in rotated channel order (DualInv): sum(px^2) per channel, min / max of the separately coded
-// channel, and the refiner's sums of the pre-weighted pixels sum(x * w) -- ContributeUnweightedPW adds the same 16 values
-// in the same order whatever the indexes are (EndpointRefiner.h:78-92), so the sum is taken once per block.
-// They wait in LDS (rows of 16 words, one word per block of the wave) and are read where they are used -- the pixel loop of
-// the search is the place with the fewest registers to spare: `rowSq[ch]` / `rowVs[ch]` = word offset of channel position
-// ch's sum(px^2) / refiner sum, `minMax` = min | max << 8 of the separately coded channel.
-// `sP`: the block's pixels in LDS, channel-major and already in rotated channel order: four words (channel positions 0..3)
-// per group g of four pixels, read again in every round (one 128-bit load per group) instead of living in 16 registers.
-__device__ __forceinline__ void evalDualFast(const u32 *sP, const DualInv &inv, int mode, int indexSelector, const Unfinished &uRGB,
-                                             int numTweak, const float (&rw)[4], const float (&rwSq)[4],
-                                             const float (&rrcpW)[4], u32 flags, const CvttDeviceTables *__restrict__ T,
-                                             int numRefine, int lane, ShapeBest &bestRGB, ShapeBest &bestA)
-{
-    const int c = lane & 3;
-    int rgbPrec, alphaPrec;
-    if (mode == 4)
-    {
-        rgbPrec = indexSelector ? 3 : 2;
-        alphaPrec = indexSelector ? 2 : 3;
-    }
-    else
-        rgbPrec = alphaPrec = 2;
-    const float rgbMax = (float)((1 << rgbPrec) - 1), alphaMaxV = (float)((1 << alphaPrec) - 1);
-    const float rgbRcpMax = T->rcpMaxIndex[rgbPrec], alphaRcpMax = T->rcpMaxIndex[alphaPrec];
-    const float wRcp16 = T->rcpTable[16];
-    const bool uniformErr = (flags & CVTTMI_FLAG_UNIFORM) != 0;
-
-    bestRGB.err = bestA.err = FLT_MAX;
-    bestRGB.ep0 = bestRGB.ep1 = bestRGB.idxLo = bestRGB.idxHi = 0;
-    bestA.ep0 = bestA.ep1 = bestA.idxLo = bestA.idxHi = 0;
-
-    const int alphaMin = (int)(inv.minMax & 0xffu), alphaMax = (int)(inv.minMax >> 8);
-
-    const int tweak = c;
-    if (tweak < numTweak)
-    {
-        int ep[2][4];
-        {
-            const float tf0 = T->tweakFactors[rgbPrec - 2][tweak][0];
-            const float tf1 = T->tweakFactors[rgbPrec - 2][tweak][1];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++)
-            {
-                ep[0][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf0, 255.0f);
-                ep[1][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf1, 255.0f);
-            }
-            // TweakAlpha (reference BC67.cpp:815-827)
-            const float af0 = T->tweakFactors[alphaPrec - 2][tweak][0];
-            const float af1 = T->tweakFactors[alphaPrec - 2][tweak][1];
-            const float base = (float)alphaMin;
-            const float offs = (float)alphaMax - base;
-            ep[0][3] = (int)clampRound(base + offs * af0, 255.0f);
-            ep[1][3] = (int)clampRound(base + offs * af1, 255.0f);
-        }
-
-        for (int refine = 0; refine < numRefine; refine++)
-        {
-            const bool last = (refine == numRefine - 1);
-            // CompressEndpoints4 / 5 (reference BC67.cpp:901-923)
-            const int cb = (mode == 4) ? 5 : 7;
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-            {
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    ep[j][ch] = unquantize(quantizeNoP(ep[j][ch], cb), cb);
-                if (mode == 4)
-                    ep[j][3] = unquantize(quantizeNoP(ep[j][3], 6), 6);
-            }
-
-            // IndexSelector<3> (rotated weights) and IndexSelector<1> (weight 1.0)
-            float origin[4], axis[4];
-            u32 tabLo[4], tabHi[4];
-            {
-                float epDW[3];
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                {
-                    origin[ch] = (float)ep[0][ch];
-                    epDW[ch] = ((float)ep[1][ch] - origin[ch]) * rw[ch];
-                }
-                float lenSq = epDW[0] * epDW[0];
-                lenSq = lenSq + epDW[1] * epDW[1];
-                lenSq = lenSq + epDW[2] * epDW[2];
-                lenSq = safeDenom(lenSq);
-                const float mvdls = rgbMax / lenSq;
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    axis[ch] = epDW[ch] * rw[ch] * mvdls;
-                origin[3] = (float)ep[0][3];
-                const float aDW = (float)ep[1][3] - origin[3];
-                const float aLen = safeDenom(aDW * aDW);
-                axis[3] = aDW * (alphaMaxV / aLen);
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    levelTable(ep[0][ch], ep[1][ch], rgbPrec == 3, tabLo[ch], tabHi[ch]);
-                levelTable(ep[0][3], ep[1][3], alphaPrec == 3, tabLo[3], tabHi[3]);
-            }
-            const v2f org01 = {origin[0], origin[1]}, org23 = {origin[2], origin[3]};
-            const v2f ax01 = {axis[0], axis[1]}, ax23 = {axis[2], axis[3]};
-            const v2f w01 = {rw[0], rw[1]}, w23 = {rw[2], 1.0f};
-            const v2f rcpMax2 = {rgbRcpMax, alphaRcpMax};
-
-            u32 s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-            v2f tv01 = {0.0f, 0.0f}, tv23 = {0.0f, 0.0f};
-            v2f tt2 = {0.0f, 0.0f}, ts2 = {0.0f, 0.0f}; // {RGB plane, alpha plane}
-            u32 rgbLo = 0, rgbHi = 0, aLo = 0, aHi = 0; // 4 bits per pixel
-
-            // an address the optimiser cannot see through: the loads stay inside the round (hoisted, they would hold 16
-            // registers again, and the 64 conversions with them)
-            const u32 *sPr = sP;
-            asm volatile("" : "+v"(sPr));
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-            {
-                u32 iR4 = 0, iA4 = 0;
-                const uint4 L = *reinterpret_cast<const uint4 *>(sPr + 4 * g);
-                const u32 Pg[4] = {L.x, L.y, L.z, L.w};
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                {
-                    const v2f x01 = {byteF(Pg[0], k), byteF(Pg[1], k)}, x23 = {byteF(Pg[2], k), byteF(Pg[3], k)};
-                    const v2f p01 = (x01 - org01) * ax01, p23 = (x23 - org23) * ax23;
-                    float dist = p01.x + p01.y;
-                    dist = dist + p23.x;
-                    // clampRound in two halves.  The last round's index goes to v_cvt_pk_u8_f32 alone, which rounds to nearest even
-                    // and saturates at 0 itself: the upper clamp is all it needs (clampHigh, cvtt_kernel_common.h).  The other
-                    // rounds' index also weights the refiner and takes the rest: clampRound(v, hi) = rintf(fmaxf(clampHigh(v, hi), 0)).
-                    float fRGB = clampHigh(dist, rgbMax);
-                    float fA = clampHigh(p23.y, alphaMaxV);
-                    if (!last)
-                    {
-                        fRGB = rintf(fmaxf(fRGB, 0.0f));
-                        fA = rintf(fmaxf(fA, 0.0f));
-                    }
-                    // the indexes are small integers: v_cvt_pk_u8_f32 converts and files one as byte k in one instruction
-                    iR4 = __builtin_amdgcn_cvt_pk_u8_f32(fRGB, (u32)k, iR4);
-                    iA4 = __builtin_amdgcn_cvt_pk_u8_f32(fA, (u32)k, iA4);
-                    if (!last)
-                    {
-                        // EndpointRefiner<3> with the rotated weights and EndpointRefiner<1> with weight 1; the sums of the
-                        // pre-weighted pixels themselves (vs) do not depend on the indexes: DualInv
-                        const v2f f2 = {fRGB, fA};
-                        const v2f t2 = f2 * rcpMax2;
-                        const v2f tt = {t2.x, t2.x};
-                        const v2f v01 = x01 * w01, v23 = x23 * w23;
-                        tv01 = tv01 + tt * v01;
-                        tv23 = tv23 + t2 * v23;
-                        tt2 = tt2 + t2 * t2;
-                        ts2 = ts2 + t2;
-                    }
-                }
-                if (g < 2)
-                {
-                    rgbLo |= nibblesOf(iR4) << (16 * g);
-                    aLo |= nibblesOf(iA4) << (16 * g);
-                }
-                else
-                {
-                    rgbHi |= nibblesOf(iR4) << (16 * (g - 2));
-                    aHi |= nibblesOf(iA4) << (16 * (g - 2));
-                }
-#pragma unroll
-                for (int ch = 0; ch < 4; ch++)
-                {
-                    const u32 R = __builtin_amdgcn_perm(tabHi[ch], tabLo[ch], ch == 3 ? iA4 : iR4);
-                    s1[ch] = __builtin_amdgcn_udot4(R, Pg[ch], s1[ch], false);
-                    s2[ch] = __builtin_amdgcn_udot4(R, R, s2[ch], false);
-                }
-            }
-
-            u32 err[4];
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-                err[ch] = s2[ch] + inv.words[inv.rowSq[ch]] - 2u * s1[ch];
-            float errorRGB, errorA;
-            if (uniformErr)
-            {
-                errorRGB = (float)(int)(err[0] + err[1] + err[2]);
-                errorA = (float)(int)err[3];
-            }
-            else
-            {
-                errorRGB = (float)(int)err[0] * rwSq[0];
-                errorRGB = errorRGB + (float)(int)err[1] * rwSq[1];
-                errorRGB = errorRGB + (float)(int)err[2] * rwSq[2];
-                errorA = (float)(int)err[3] * rwSq[3];
-            }
-
-            if (errorRGB < bestRGB.err)
-            {
-                bestRGB.err = errorRGB;
-                bestRGB.ep0 = (u32)ep[0][0] | ((u32)ep[0][1] << 8) | ((u32)ep[0][2] << 16);
-                bestRGB.ep1 = (u32)ep[1][0] | ((u32)ep[1][1] << 8) | ((u32)ep[1][2] << 16);
-                bestRGB.idxLo = rgbLo;
-                bestRGB.idxHi = rgbHi;
-            }
-            if (errorA < bestA.err)
-            {
-                bestA.err = errorA;
-                bestA.ep0 = (u32)ep[0][3] << 24;
-                bestA.ep1 = (u32)ep[1][3] << 24;
-                bestA.idxLo = aLo;
-                bestA.idxHi = aHi;
-            }
-
-            if (!last)
-            {
-                // EndpointRefiner<3> / <1>::GetRefinedEndpointsLDR, 16 contributions each
-                const float tv[4] = {tv01.x, tv01.y, tv23.x, tv23.y};
-                const float vs[4] = {__builtin_bit_cast(float, inv.words[inv.rowVs[0]]), __builtin_bit_cast(float, inv.words[inv.rowVs[1]]),
-                                     __builtin_bit_cast(float, inv.words[inv.rowVs[2]]), __builtin_bit_cast(float, inv.words[inv.rowVs[3]])};
-                {
-                    const float ttRGB = tt2.x, tsRGB = ts2.x;
-                    float adenom = (ttRGB * 16.0f - tsRGB * tsRGB) * wRcp16;
-                    const bool z = (adenom == 0.0f);
-                    if (z) adenom = 1.0f;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ch++)
-                    {
-                        const float a = (tv[ch] - tsRGB * vs[ch] * wRcp16) / adenom;
-                        const float b = (vs[ch] - a * tsRGB) * wRcp16;
-                        float p1 = b, p2 = a + b;
-                        if (z)
-                        {
-                            p1 = vs[ch] * wRcp16;
-                            p2 = p1;
-                        }
-                        ep[0][ch] = (int)clampRound(p1 * rrcpW[ch], 255.0f);
-                        ep[1][ch] = (int)clampRound(p2 * rrcpW[ch], 255.0f);
-                    }
-                }
-                {
-                    const float ttA = tt2.y, tsA = ts2.y;
-                    float adenom = (ttA * 16.0f - tsA * tsA) * wRcp16;
-                    const bool z = (adenom == 0.0f);
-                    if (z) adenom = 1.0f;
-                    const float a = (tv[3] - tsA * vs[3] * wRcp16) / adenom;
-                    const float b = (vs[3] - a * tsA) * wRcp16;
-                    float p1 = b, p2 = a + b;
-                    if (z)
-                    {
-                        p1 = vs[3] * wRcp16;
-                        p2 = p1;
-                    }
-                    ep[0][3] = (int)clampRound(p1, 255.0f);
-                    ep[1][3] = (int)clampRound(p2, 255.0f);
-                }
-            }
-        }
-    }
-    quadArgminBroadcast(bestRGB, lane);
-    quadArgminBroadcast(bestA, lane);
-}
-
-// =====================================================================================
-// Exact branch-and-bound, part 2: cheap bounds for every partition before anything is
-// searched (part 1, the bound itself, is shapeErrorLowerBound in cvtt_kernel_common.h).
-//
-// The weighted pixels of a block are projected on an orthonormal pair (e1, e2) -- the two
-// leading principal axes of the whole block, so that little of any subset's residual is lost --
-// scaled and rounded to 12-bit integers.  An orthogonal projection never increases distances,
-// so the total-least-squares residual of the projected, rounded points (minus the allowance
-// for the rounding radius) still bounds the error of every trial from below; in 2-D the
-// residual is the smaller eigenvalue of a 2x2 matrix whose entries are exact integers
-// accumulated with v_dot2_i32_i16 over a per-lane pixel mask.  Sub-lane c of a quad walks
-// partitions c, c+4, ...; the bounds land in LDS (64 partitions x 16 blocks).
-// =====================================================================================
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int dot2(u32 a, u32 b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, a), __builtin_bit_cast(v2s, b), acc, false);
-}
-
-__device__ __forceinline__ constexpr int tri(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-
-struct BlockScatter
-{
-    float S[10];     // weighted scatter matrix of the 16 pixels (lower triangle, row-major)
-    float meanW[4];  // weighted centroid
-};
-
-// raw sums of the 16 pixels: s[ch] = sum x, p[tri(r, c)] = sum x_r x_c
-__device__ __forceinline__ void blockRawSums(const u32 (&pix)[16], int (&s)[4], int (&p)[10])
-{
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        s[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        p[i] = 0;
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-    {
-        const u32 pk = fetchPixel(pix[px]);
-        int x[4];
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            x[ch] = byteI(pk, ch);
-            s[ch] += x[ch];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int c = 0; c <= r; c++)
-                p[tri(r, c)] = mad24(x[r], x[c], p[tri(r, c)]);
-    }
-}
-
-// the same, by the four lanes of the quad that holds the block: sub-lane c sums pixels c, c+4, c+8, c+12 and the quad adds up
-__device__ __forceinline__ void blockRawSumsQuad(const u32 (&pix)[16], int c, int (&s)[4], int (&p)[10])
-{
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        s[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        p[i] = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-    {
-        const u32 p0 = pix[4 * j], p1 = pix[4 * j + 1], p2 = pix[4 * j + 2], p3 = pix[4 * j + 3];
-        const u32 pk = fetchPixel(c == 0 ? p0 : c == 1 ? p1 : c == 2 ? p2 : p3);
-        int x[4];
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            x[ch] = byteI(pk, ch);
-            s[ch] += x[ch];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int cc = 0; cc <= r; cc++)
-                p[tri(r, cc)] = mad24(x[r], x[cc], p[tri(r, cc)]);
-    }
-#pragma unroll
-    for (int step = 1; step <= 2; step <<= 1)
-    {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            s[i] += xorLane(s[i], step);
-#pragma unroll
-        for (int i = 0; i < 10; i++)
-            p[i] += xorLane(p[i], step);
-    }
-}
-
-__device__ __forceinline__ void scatterFromRaw(const int (&s)[4], const int (&p)[10], const CvttBc7Args &A, BlockScatter &bs)
-{
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-    {
-        bs.meanW[r] = (float)s[r] * A.w[r] * 0.0625f;
-#pragma unroll
-        for (int c = 0; c <= r; c++)
-        {
-            // 16*sum(xy) - sum(x)*sum(y): an exact integer below 2^24
-            const int v = 16 * p[tri(r, c)] - __mul24(s[r], s[c]);
-            // (no product of two weights on its own: the optimiser would keep all ten of them in registers for the whole kernel)
-            bs.S[tri(r, c)] = (((float)v * 0.0625f) * A.w[r]) * A.w[c];
-        }
-    }
-}
-
-// Exact branch-and-bound, second tier: the bound of a subset in all of its channels.  The 2-D projection of the first
-// tier keeps one of the three (two) residual directions of a subset; on low-variance content with noise in every
-// channel that leaves most partitions alive.  Raw integer sums of the member pixels of a subset -> scatter matrix ->
-// shapeErrorLowerBound, for the partitions that survived the first tier only.
-struct RawSums
-{
-    int n;
-    int s[4];
-    int p[10];
-};
-
-__device__ __forceinline__ void maskedRawSums(const u32 (&pix)[16], u32 mask, RawSums &r)
-{
-    r.n = __popc(mask & 0xffffu);
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        r.s[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        r.p[i] = 0;
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-    {
-        // a pixel that is not a member counts as (0, 0, 0, 0)
-        const u32 pk = fetchPixel(pix[px]) & (u32)__builtin_amdgcn_sbfe(mask, px, 1);
-        int x[4];
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            x[ch] = byteI(pk, ch);
-            r.s[ch] += x[ch];
-        }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b <= a; b++)
-                r.p[tri(a, b)] = mad24(x[a], x[b], r.p[tri(a, b)]);
-    }
-}
-
-// channel-major copy of a block: P[ch][g] = channel ch of pixels 4g .. 4g+3 (the layout of the dual-plane search)
-__device__ __forceinline__ void channelMajor(const u32 (&pix)[16], u32 (&P)[4][4])
-{
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-    {
-        const u32 a = fetchPixel(pix[4 * g]), b = fetchPixel(pix[4 * g + 1]), cc = fetchPixel(pix[4 * g + 2]), d = fetchPixel(pix[4 * g + 3]);
-        const u32 ab02 = __builtin_amdgcn_perm(b, a, 0x06020400u); // a0 b0 a2 b2
-        const u32 ab13 = __builtin_amdgcn_perm(b, a, 0x07030501u); // a1 b1 a3 b3
-        const u32 cd02 = __builtin_amdgcn_perm(d, cc, 0x06020400u);
-        const u32 cd13 = __builtin_amdgcn_perm(d, cc, 0x07030501u);
-        P[0][g] = __builtin_amdgcn_perm(cd02, ab02, 0x05040100u); // a0 b0 c0 d0
-        P[2][g] = __builtin_amdgcn_perm(cd02, ab02, 0x07060302u); // a2 b2 c2 d2
-        P[1][g] = __builtin_amdgcn_perm(cd13, ab13, 0x05040100u);
-        P[3][g] = __builtin_amdgcn_perm(cd13, ab13, 0x07060302u);
-    }
-}
-
-// the same sums from the channel-major copy: four pixels per v_dot4_u32_u8
-__device__ __forceinline__ void maskedRawSumsCM(const u32 (&P)[4][4], u32 mask, RawSums &r)
-{
-    r.n = __popc(mask & 0xffffu);
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        r.s[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        r.p[i] = 0;
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-    {
-        // four mask bits -> four 0x00 / 0xff bytes
-        const u32 bits = (((mask >> (4 * g)) & 0xfu) * 0x00204081u) & 0x01010101u;
-        const u32 sel = (bits << 8) - bits;
-        u32 m[4];
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-        {
-            m[ch] = P[ch][g] & sel;
-            r.s[ch] = (int)__builtin_amdgcn_udot4(m[ch], 0x01010101u, (u32)r.s[ch], false);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b <= a; b++)
-                r.p[tri(a, b)] = (int)__builtin_amdgcn_udot4(m[a], P[b][g], (u32)r.p[tri(a, b)], false);
-    }
-}
-
-__device__ __forceinline__ void rawSumsSub(RawSums &d, const RawSums &a)
-{
-    d.n -= a.n;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        d.s[i] -= a.s[i];
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        d.p[i] -= a.p[i];
-}
-
-// n*sum(xy) - sum(x)*sum(y) is an exact integer below 2^24, so the matrix entries carry the rounding of two float
-// products only, which the margins of shapeErrorLowerBound cover
-template <int N>
-__device__ __forceinline__ float subsetBoundFull(const RawSums &r, const float (&w)[4], float delta)
-{
-    if (r.n < 2)
-        return 0.0f;
-    const float n = (float)r.n;
-    const float inv = __builtin_amdgcn_rcpf(n);
-    Moments<N> m;
-#pragma unroll
-    for (int a = 0; a < N; a++)
-#pragma unroll
-        for (int b = 0; b <= a; b++)
-        {
-            const int v = __mul24(r.n, r.p[tri(a, b)]) - __mul24(r.s[a], r.s[b]);
-            m.cov[tri(a, b)] = (((float)v * inv) * w[a]) * w[b]; // see scatterFromRaw
-        }
-    return shapeErrorLowerBound<N>(m, n, delta);
-}
-
-// dominant eigenvector of a symmetric PSD 4x4 (power iteration from the column of the
-// largest diagonal entry).  Accuracy only affects how tight the bounds are, never their
-// validity: the caller orthonormalises whatever comes back.
-__device__ __forceinline__ void topEigenvector(const float (&M)[10], float (&e)[4])
-{
-    int k = 0;
-    float d = M[tri(0, 0)];
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (M[tri(i, i)] > d)
-        {
-            d = M[tri(i, i)];
-            k = i;
-        }
-    float v[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        v[i] = (k == 0) ? M[tri(i, 0)] : (k == 1) ? M[tri(i, 1)] : (k == 2) ? M[tri(i, 2)] : M[tri(i, 3)];
-    for (int it = 0; it < CVTT_EIG_ITERS; it++)
-    {
-        float nv[4];
-        float big = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-        {
-            float a = M[tri(r, 0)] * v[0];
-#pragma unroll
-            for (int c = 1; c < 4; c++)
-                a = __fmaf_rn(M[tri(r, c)], v[c], a);
-            nv[r] = a;
-            big = fmaxf(big, fabsf(a));
-        }
-        const float sc = (big > 0.0f) ? __builtin_amdgcn_rcpf(big) : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            v[r] = nv[r] * sc;
-    }
-    float len = v[0] * v[0];
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        len = __fmaf_rn(v[i], v[i], len);
-    const bool ok = len > 1e-12f && len < 1e12f; // false for 0 and NaN
-    const float inv = ok ? __builtin_amdgcn_rsqf(len) : 0.0f;
-    e[0] = ok ? v[0] * inv : 1.0f;
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        e[i] = v[i] * inv;
-}
-
-// Second tier, sharpened ("Soundness of the bounds", part 3).  The bound above treats a trial as ANY line plus
-// the worst rounding of the reconstructed colours (delta = 0.5 * |w|, as if every rounding pointed at the pixel).  Two facts
-// about the trials tighten it, both stated for an arbitrary unit vector d (here: the subset's principal direction from a few
-// power iterations -- its accuracy affects only how tight the result is):
-//  * Rounding moves a reconstructed colour by at most 0.5 * w_ch per channel, and only the part of that ACROSS the trial's
-//    line lowers the error.  For a line along u the largest such part is s(u) = 0.5 * sqrt(|w|^2 - min_sigma (u . (sigma w))^2)
-//    (sigma = sign patterns).  With the default channel weights (green and alpha dominate) and a line that follows green, s is
-//    0.16 instead of 0.52.
-//  * The reconstructed colours of a subset are only 2^indexBits points of the line.  Projected on d the pixels are therefore
-//    approximated by that many values: Q_d = the cost of the best clustering of the projections into 2^indexBits groups
-//    (sum of squared distances to the group means).  It is computed for the two-bit modes, exactly: the projections are
-//    sorted (the groups of an optimal clustering in one dimension are runs) and a dynamic programme places the boundaries.
-// A trial whose line u makes the angle asin(beta) with d (u = alpha d + beta v, v _|_ d) has, before rounding,
-//    error >= alpha^2 R_d + beta^2 L_d - 2 alpha beta rho + max(0, alpha sqrt(Q_d) - beta sqrt(R_d))^2,
-// L_d = d^T S d, R_d = trace(S) - L_d (>= v^T S v), rho = |S d - L_d d| (>= |d^T S v|); the last term is the distance of the
-// projections on u from the (cone of) vectors with few distinct values, which differs from that of the projections on d by at
-// most beta sqrt(v^T S v).  And |u . (sigma w)| >= alpha m_d - beta sqrt(|w|^2 - m_d^2) with m_d = min_sigma |d . (sigma w)|
-// (>= 2 max_ch - sum_ch of |d_ch| w_ch).  [0, 1] is cut into a few intervals of beta; on each, every term is replaced by its worst
-// value there, G - 2 s sqrt(n G) is formed as in the first bound, and the minimum over the intervals is the result.  Margins:
-// every quantity that comes from a cancellation is moved by 1e-5 * trace(S) in the safe direction (the float error of S, of d's
-// length and of the products is below 2e-6 of it), the projections by 2e-3, the result is scaled by 0.9999.
-// (lp: the block's sixteen pixels in LDS.  They are read twice, for the sums and for the projections, rather than kept in
-// registers in between: this function is the register peak of the bounds.)
-template <int N>
-__device__ __forceinline__ float subsetBoundSharp(const u32 *lp, u32 mask, const float (&w)[4], float delta, float wSq, bool fourLevels)
-{
-    RawSums r;
-    {
-        asm volatile("" : "+v"(lp));
-        u32 px[16], CM[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-        {
-            const uint4 v = *reinterpret_cast<const uint4 *>(lp + 4 * i);
-            px[4 * i + 0] = v.x;
-            px[4 * i + 1] = v.y;
-            px[4 * i + 2] = v.z;
-            px[4 * i + 3] = v.w;
-        }
-        channelMajor(px, CM);
-        maskedRawSumsCM(CM, mask, r);
-    }
-    if (r.n < 2)
-        return 0.0f;
-    const float n = (float)r.n;
-    const float inv = __builtin_amdgcn_rcpf(n);
-    Moments<N> m;
-#pragma unroll
-    for (int a = 0; a < N; a++)
-#pragma unroll
-        for (int b = 0; b <= a; b++)
-        {
-            const int v = __mul24(r.n, r.p[tri(a, b)]) - __mul24(r.s[a], r.s[b]);
-            m.cov[tri(a, b)] = (((float)v * inv) * w[a]) * w[b]; // see scatterFromRaw
-        }
-    float rTrue;
-    const float cur = shapeErrorLowerBound<N>(m, n, delta, &rTrue);
-    if (r.n < 3 || !(rTrue >= 0.0f))
-        return cur;
-    float T = 0.0f;
-#pragma unroll
-    for (int i = 0; i < N; i++)
-        T += m.cov[tri(i, i)];
-    float e[4];
-    {
-        float M[10];
-#pragma unroll
-        for (int i = 0; i < 10; i++)
-            M[i] = (N == 4 || i < 6) ? m.cov[i < N * (N + 1) / 2 ? i : 0] : 0.0f;
-        topEigenvector(M, e);
-    }
-    float L = 0.0f, Sd[N];
-#pragma unroll
-    for (int a = 0; a < N; a++)
-    {
-        float acc = 0.0f;
-#pragma unroll
-        for (int b = 0; b < N; b++)
-            acc = __fmaf_rn(m.cov[a >= b ? tri(a, b) : tri(b, a)], e[b], acc);
-        Sd[a] = acc;
-        L = __fmaf_rn(e[a], acc, L);
-    }
-    float rho2 = 0.0f, aMax = 0.0f, aSum = 0.0f;
-#pragma unroll
-    for (int a = 0; a < N; a++)
-    {
-        const float t = Sd[a] - L * e[a];
-        rho2 = __fmaf_rn(t, t, rho2);
-        const float ac = fabsf(e[a]) * w[a];
-        aMax = fmaxf(aMax, ac);
-        aSum += ac;
-    }
-    const float eta = 1e-5f * T;
-    const float Llo = fmaxf(L - eta, 0.0f);
-    const float Rlo = fmaxf(T - L - eta, 0.0f);
-    const float sqrtRhi = __builtin_amdgcn_sqrtf(fmaxf(T - L, 0.0f) + eta) * 1.000001f;
-    const float rhoHi = __builtin_amdgcn_sqrtf(rho2) * 1.000001f + eta;
-    const float W2 = wSq * 1.000001f;
-    const float md = fmaxf(2.0f * aMax - aSum, 0.0f) * 0.99999f;
-    const float perp = __builtin_amdgcn_sqrtf(fmaxf(W2 - md * md, 0.0f)) * 1.000001f;
-
-    float sqrtQ = 0.0f;
-    constexpr int kMaxN = 13; // the largest subset of any BC7 partition (a larger one would simply go without Q_d)
-    if (fourLevels && r.n > 4 && r.n <= kMaxN)
-    {
-        float g[4];
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-            g[ch] = (ch < N) ? e[ch] * w[ch] : 0.0f;
-        float t[16];
-        asm volatile("" : "+v"(lp));
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-        {
-            const uint4 v = *reinterpret_cast<const uint4 *>(lp + 4 * q);
-            const u32 pw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-            {
-                float a = 0.0f;
-#pragma unroll
-                for (int ch = 0; ch < N; ch++)
-                    a = __fmaf_rn(g[ch], byteF(pw[k], ch), a);
-                t[4 * q + k] = ((mask >> (4 * q + k)) & 1u) ? a : 1e30f;
-            }
-        }
-        // Batcher's merge exchange, 63 comparators: the members come first, in ascending order
-#define CE(a, b) { const float lo_ = fminf(t[a], t[b]); t[b] = fmaxf(t[a], t[b]); t[a] = lo_; }
-        CE(0,1) CE(2,3) CE(4,5) CE(6,7) CE(8,9) CE(10,11) CE(12,13) CE(14,15) CE(0,2) CE(1,3) CE(4,6) CE(5,7) CE(8,10) CE(9,11) CE(12,14) CE(13,15)
-        CE(1,2) CE(5,6) CE(9,10) CE(13,14) CE(0,4) CE(1,5) CE(2,6) CE(3,7) CE(8,12) CE(9,13) CE(10,14) CE(11,15) CE(2,4) CE(3,5) CE(10,12) CE(11,13)
-        CE(1,2) CE(3,4) CE(5,6) CE(9,10) CE(11,12) CE(13,14) CE(0,8) CE(1,9) CE(2,10) CE(3,11) CE(4,12) CE(5,13) CE(6,14) CE(7,15) CE(4,8) CE(5,9)
-        CE(6,10) CE(7,11) CE(2,4) CE(3,5) CE(6,8) CE(7,9) CE(10,12) CE(11,13) CE(1,2) CE(3,4) CE(5,6) CE(7,8) CE(9,10) CE(11,12) CE(13,14)
-#undef CE
-        // The exact cost of the best clustering of the sorted projections into four groups, by dynamic programming over the
-        // group boundaries: D_k[j] = min_i D_(k-1)[i] + cost(i, j), cost(i, j) = sum t^2 - (sum t)^2 / (j - i) over t[i .. j-1]
-        // (empty groups allowed: D_k[0] = 0).  Everything is unrolled over the kMaxN slots a subset can fill, the slots past the
-        // members hold zeros after the shift by t[0], and the last group is taken from suffix sums so that no step depends on
-        // the (per-lane) member count.
-        const int cnt = r.n;
-        const float t0 = t[0];
-        float range = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kMaxN; j++)
-        {
-            t[j] = (j < cnt) ? t[j] - t0 : 0.0f;
-            range = fmaxf(range, t[j]);
-        }
-        constexpr float kRcp[17] = {0.0f, 1.0f, 1.0f / 2, 1.0f / 3, 1.0f / 4, 1.0f / 5, 1.0f / 6, 1.0f / 7, 1.0f / 8, 1.0f / 9, 1.0f / 10, 1.0f / 11, 1.0f / 12,
-                                    1.0f / 13, 1.0f / 14, 1.0f / 15, 1.0f / 16};
-        float D2[kMaxN + 1], D3[kMaxN + 1];
-        D2[0] = D3[0] = 0.0f;
-        {
-            float su = 0.0f, sq = 0.0f;
-#pragma unroll
-            for (int j = 1; j <= kMaxN; j++)
-            {
-                su += t[j - 1];
-                sq = __fmaf_rn(t[j - 1], t[j - 1], sq);
-                D2[j] = D3[j] = __fmaf_rn(-su * su, kRcp[j], sq); // one group: D_1[j]
-            }
-        }
-        float fin = D3[kMaxN]; // (zeros past the members: an over-estimate of the one-group cost of all of them, harmless in a minimum)
-        {
-            float su0 = 0.0f, sq0 = 0.0f; // prefix sums: D_1[i]
-#pragma unroll
-            for (int i = 1; i < kMaxN; i++)
-            {
-                su0 += t[i - 1];
-                sq0 = __fmaf_rn(t[i - 1], t[i - 1], sq0);
-                const float d1 = __fmaf_rn(-su0 * su0, kRcp[i], sq0);
-                const float d2 = D2[i], d3 = D3[i]; // final: every start below i has been through
-                float su = 0.0f, sq = 0.0f;
-#pragma unroll
-                for (int j = i + 1; j <= kMaxN; j++)
-                {
-                    su += t[j - 1];
-                    sq = __fmaf_rn(t[j - 1], t[j - 1], sq);
-                    const float cst = __fmaf_rn(-su * su, kRcp[j - i], sq);
-                    D2[j] = fminf(D2[j], d1 + cst);
-                    D3[j] = fminf(D3[j], d2 + cst);
-                }
-                // the fourth group, t[i .. cnt-1]: su / sq now hold the sums of everything from i on (zeros past the members)
-                const float m = (float)(cnt - i);
-                const float last = __fmaf_rn(-su * su, __builtin_amdgcn_rcpf(m), sq); // (v_rcp_f32: 1 ulp, inside the margin below)
-                fin = (i < cnt) ? fminf(fin, d3 + last) : fin;
-            }
-        }
-        // float error of a cost: a few ulps of (count * range^2); four of them and the running minima
-        const float Q = fmaxf(fin - 2e-5f * range * range, 0.0f);
-        sqrtQ = fmaxf(__builtin_amdgcn_sqrtf(fmaxf(Q * 0.9999f, 0.0f)) - 2e-3f, 0.0f);
-    }
-
-    // beta = 0, 0.01, 0.02, 0.03, 0.04, 0.055, 0.07, 0.085, 0.1, 0.125, 0.15, 0.175, 0.2, 0.25, 0.3, 0.375, 0.45, 0.55, 0.7, 0.85, 1: dense
-    // where the minimum usually is (a small angle buys a lot of rounding slack when d is close to the dominant channel)
-    constexpr int kIntervals = 20;
-    constexpr float kB0sq[20] = {0.0f, 0.0001f, 0.0004f, 0.0009f, 0.0016f, 0.003025f, 0.0049f, 0.007225f, 0.01f, 0.015625f, 0.0225f, 0.030625f, 0.04f, 0.0625f, 0.09f, 0.140625f, 0.2025f, 0.3025f, 0.49f, 0.7225f};
-    constexpr float kB1sq[20] = {0.0001f, 0.0004f, 0.0009f, 0.0016f, 0.003025f, 0.0049f, 0.007225f, 0.01f, 0.015625f, 0.0225f, 0.030625f, 0.04f, 0.0625f, 0.09f, 0.140625f, 0.2025f, 0.3025f, 0.49f, 0.7225f, 1.0f};
-    constexpr float kB1[20] = {0.01f, 0.02f, 0.03f, 0.04f, 0.055f, 0.07f, 0.085f, 0.1f, 0.125f, 0.15f, 0.175f, 0.2f, 0.25f, 0.3f, 0.375f, 0.45f, 0.55f, 0.7f, 0.85f, 1.0f};
-    // sqrt(1 - beta1^2), rounded down
-    constexpr float kA1[20] = {0.999948f, 0.999798f, 0.9995479f, 0.9991977f, 0.9984844f, 0.997545f, 0.996379f, 0.9949854f, 0.9921548f, 0.988684f, 0.9845665f, 0.9797939f, 0.9682439f, 0.9539373f, 0.927023f, 0.8930268f, 0.835163f, 0.7141414f, 0.5267816f, 0.0f};
-    // the largest alpha * beta of the interval, rounded up
-    constexpr float kCross[20] = {0.00999952f, 0.01999604f, 0.02998656f, 0.03996807f, 0.05491686f, 0.06982843f, 0.08469255f, 0.09949894f, 0.1240198f, 0.1483032f, 0.1722998f, 0.1959596f, 0.2420619f, 0.2861823f, 0.347635f, 0.4018637f, 0.4593415f, 0.499901f, 0.500001f, 0.4477662f};
-    float best = FLT_MAX;
-#pragma unroll
-    for (int j = 0; j < kIntervals; j++)
-    {
-        const float e0 = __fmaf_rn(kB0sq[j], Llo - Rlo, Rlo), e1 = __fmaf_rn(kB1sq[j], Llo - Rlo, Rlo);
-        float base = fminf(e0, e1) * 0.999999f - 2.0f * kCross[j] * rhoHi;
-        base = fmaxf(base, rTrue);
-        const float qd = fmaxf(kA1[j] * sqrtQ - kB1[j] * sqrtRhi, 0.0f);
-        const float G = __fmaf_rn(qd, qd, base);
-        const float inner = fmaxf(kA1[j] * md - kB1[j] * perp, 0.0f);
-        const float s2 = 0.25f * (W2 - inner * inner) * 1.000001f;
-        float v = 0.0f;
-        if (G > 4.0001f * n * s2)
-            v = G - 2.0f * __builtin_amdgcn_sqrtf(s2 * n * G) * 1.000001f;
-        best = fminf(best, v);
-    }
-    return fmaxf(cur, best * 0.9999f);
-}
-
-__device__ __forceinline__ int dot4s(u32 a, u32 b, int acc) { return __builtin_amdgcn_sdot4((int)a, (int)b, acc, false); }
-template <bool G8>
-struct Proj2D
-{
-    // G8: int8 quadruples, pixel 4k + j in byte j; else int16 pairs, pixel 2k in the low half, 2k+1 in the high half
-    u32 U[G8 ? 4 : 8], V[G8 ? 4 : 8];
-    int tU, tV, tUU, tVV, tUV; // sums over all 16 pixels
-};
-
-// Project the block on its two leading principal axes (channels 0..2 only when !use4).
-template <bool G8>
-__device__ __forceinline__ void makeProjection(const u32 (&pix)[16], const BlockScatter &bs, const CvttBc7Args &A,
-                                               bool use4, float scale, Proj2D<G8> &P)
-{
-    float M[10];
-#pragma unroll
-    for (int i = 0; i < 10; i++)
-        M[i] = (use4 || i < 6) ? bs.S[i] : 0.0f;
-    float e1[4], e2[4];
-    topEigenvector(M, e1);
-    {
-        // deflate: M -= lambda e1 e1^T
-        float Me[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-        {
-            float a = M[tri(r, 0)] * e1[0];
-#pragma unroll
-            for (int c = 1; c < 4; c++)
-                a = __fmaf_rn(M[tri(r, c)], e1[c], a);
-            Me[r] = a;
-        }
-        float lam = Me[0] * e1[0];
-#pragma unroll
-        for (int r = 1; r < 4; r++)
-            lam = __fmaf_rn(Me[r], e1[r], lam);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int c = 0; c <= r; c++)
-                M[tri(r, c)] = __fmaf_rn(-lam * e1[r], e1[c], M[tri(r, c)]);
-    }
-    topEigenvector(M, e2);
-    {
-        // Gram-Schmidt against e1; when nothing is left take the coordinate axis e1 leans on least
-        float d = e2[0] * e1[0];
-#pragma unroll
-        for (int i = 1; i < 4; i++)
-            d = __fmaf_rn(e2[i], e1[i], d);
-        float len = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-        {
-            e2[i] = __fmaf_rn(-d, e1[i], e2[i]);
-            len = __fmaf_rn(e2[i], e2[i], len);
-        }
-        if (!(len > 1e-4f))
-        {
-            int k = 0;
-            float small = fabsf(e1[0]);
-#pragma unroll
-            for (int i = 1; i < 4; i++)
-                if ((use4 || i < 3) && fabsf(e1[i]) < small)
-                {
-                    small = fabsf(e1[i]);
-                    k = i;
-                }
-            const float ek = (k == 0) ? e1[0] : (k == 1) ? e1[1] : (k == 2) ? e1[2] : e1[3];
-            len = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-            {
-                e2[i] = ((i == k) ? 1.0f : 0.0f) - ek * e1[i];
-                len = __fmaf_rn(e2[i], e2[i], len);
-            }
-        }
-        const float inv = __builtin_amdgcn_rsqf(len);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            e2[i] *= inv;
-    }
-    if (!use4)
-        e1[3] = e2[3] = 0.0f; // already zero up to rounding; keep alpha out exactly
-
-    float g1[4], g2[4];
-    float o1 = 0.0f, o2 = 0.0f;
-#pragma unroll
-    for (int ch = 0; ch < 4; ch++)
-    {
-        g1[ch] = e1[ch] * A.w[ch] * scale;
-        g2[ch] = e2[ch] * A.w[ch] * scale;
-        o1 = __fmaf_rn(e1[ch] * scale, bs.meanW[ch], o1);
-        o2 = __fmaf_rn(e2[ch] * scale, bs.meanW[ch], o2);
-    }
-    P.tU = P.tV = P.tUU = P.tVV = P.tUV = 0;
-    if constexpr (G8)
-    {
-    // the four lanes of a quad hold the same block: sub-lane c projects pixels 4c .. 4c+3 and the quad exchanges the words
-    int tid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); // = threadIdx.x (one wave per workgroup), recomputed:
-    asm volatile("" : "+v"(tid)); // the optimiser otherwise keeps the prologue's thread id (or `lane & ~3`) alive, spilled, for this
-    const int c = tid & 3;
-    u32 myU = 0, myV = 0;
-    {
-        u32 ub = 0, vb = 0;
-#pragma unroll
-        for (int h = 0; h < 4; h++)
-        {
-            const u32 p0 = pix[h], p1 = pix[4 + h], p2 = pix[8 + h], p3 = pix[12 + h];
-            const u32 pk = fetchPixel(c == 0 ? p0 : c == 1 ? p1 : c == 2 ? p2 : p3);
-            float fu = -o1, fv = -o2;
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-            {
-                const float x = byteF(pk, ch);
-                fu = __fmaf_rn(g1[ch], x, fu);
-                fv = __fmaf_rn(g2[ch], x, fv);
-            }
-            // clamping is a projection on a box: it never increases distances either
-            fu = fminf(fmaxf(fu, -kBoundLimit8), kBoundLimit8);
-            fv = fminf(fmaxf(fv, -kBoundLimit8), kBoundLimit8);
-            ub |= ((u32)(int)rintf(fu) & 0xffu) << (8 * h);
-            vb |= ((u32)(int)rintf(fv) & 0xffu) << (8 * h);
-        }
-        myU = ub;
-        myV = vb;
-    }
-    const int quadBase = tid & ~3;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-        const u32 ub = (u32)__shfl((int)myU, quadBase + k), vb = (u32)__shfl((int)myV, quadBase + k);
-        P.U[k] = ub;
-        P.V[k] = vb;
-        P.tU = dot4s(ub, 0x01010101u, P.tU);
-        P.tV = dot4s(vb, 0x01010101u, P.tV);
-        P.tUU = dot4s(ub, ub, P.tUU);
-        P.tVV = dot4s(vb, vb, P.tVV);
-        P.tUV = dot4s(ub, vb, P.tUV);
-    }
-    }
-    else
-    {
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-    {
-        int uu[2], vv[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++)
-        {
-            const u32 pk = fetchPixel(pix[2 * k + h]);
-            float fu = -o1, fv = -o2;
-#pragma unroll
-            for (int ch = 0; ch < 4; ch++)
-            {
-                const float x = byteF(pk, ch);
-                fu = __fmaf_rn(g1[ch], x, fu);
-                fv = __fmaf_rn(g2[ch], x, fv);
-            }
-            // clamping is a projection on a box: it never increases distances either
-            fu = fminf(fmaxf(fu, -kBoundLimit16), kBoundLimit16);
-            fv = fminf(fmaxf(fv, -kBoundLimit16), kBoundLimit16);
-            uu[h] = (int)rintf(fu);
-            vv[h] = (int)rintf(fv);
-        }
-        P.U[k] = ((u32)uu[0] & 0xffffu) | ((u32)uu[1] << 16);
-        P.V[k] = ((u32)vv[0] & 0xffffu) | ((u32)vv[1] << 16);
-        P.tU = dot2(P.U[k], 0x00010001u, P.tU);
-        P.tV = dot2(P.V[k], 0x00010001u, P.tV);
-        P.tUU = dot2(P.U[k], P.U[k], P.tUU);
-        P.tVV = dot2(P.V[k], P.V[k], P.tVV);
-        P.tUV = dot2(P.U[k], P.V[k], P.tUV);
-    }
-    }
-}
-
-struct Sums2D
-{
-    int n, u, v, uu, vv, uv;
-};
-
-// 8-bit grid, the subset given as the byte masks of CvttDeviceTables::subsetByteMask (one 16-byte load instead of four
-// nibble -> byte-mask expansions per subset: those were a third of the instructions of a first-tier bound, a quarter-rate
-// v_mul_lo_u32 among them)
-__device__ __forceinline__ void maskedSumsSel(const Proj2D<true> &P, int n, const uint4 &sel, Sums2D &m)
-{
-    m.n = n;
-    m.u = m.v = m.uu = m.vv = m.uv = 0;
-    const u32 s4[4] = {sel.x, sel.y, sel.z, sel.w};
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-        const u32 um = P.U[k] & s4[k], vm = P.V[k] & s4[k];
-        m.u = dot4s(um, 0x01010101u, m.u);
-        m.v = dot4s(vm, 0x01010101u, m.v);
-        m.uu = dot4s(um, P.U[k], m.uu);
-        m.vv = dot4s(vm, P.V[k], m.vv);
-        m.uv = dot4s(um, P.V[k], m.uv);
-    }
-}
-
-template <bool G8>
-__device__ __forceinline__ void maskedSums(const Proj2D<G8> &P, u32 mask, Sums2D &m)
-{
-    m.n = __popc(mask);
-    m.u = m.v = m.uu = m.vv = m.uv = 0;
-    if constexpr (G8)
-    {
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-        // four mask bits -> four 0x00 / 0xff bytes
-        const u32 bits = (((mask >> (4 * k)) & 0xfu) * 0x00204081u) & 0x01010101u;
-        const u32 sel = (bits << 8) - bits;
-        const u32 um = P.U[k] & sel, vm = P.V[k] & sel;
-        m.u = dot4s(um, 0x01010101u, m.u);
-        m.v = dot4s(vm, 0x01010101u, m.v);
-        m.uu = dot4s(um, P.U[k], m.uu);
-        m.vv = dot4s(vm, P.V[k], m.vv);
-        m.uv = dot4s(um, P.V[k], m.uv);
-    }
-    }
-    else
-    {
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-    {
-        const u32 lo = (u32)__builtin_amdgcn_sbfe(mask, 2 * k, 1);
-        const u32 hi = (u32)__builtin_amdgcn_sbfe(mask, 2 * k + 1, 1);
-        const u32 sel = (lo & 0x0000ffffu) | (hi & 0xffff0000u);
-        const u32 um = P.U[k] & sel, vm = P.V[k] & sel;
-        m.u = dot2(um, 0x00010001u, m.u);
-        m.v = dot2(vm, 0x00010001u, m.v);
-        m.uu = dot2(um, P.U[k], m.uu);
-        m.vv = dot2(vm, P.V[k], m.vv);
-        m.uv = dot2(um, P.V[k], m.uv);
-    }
-    }
-}
-
-// Lower bound on the error of any trial of the subset with sums `m`.  |coordinates| <= 2040 and
-// n <= 16 keep n*sum(uu) and sum(u)^2 below 2^31, so A, B, C are exact; the float steps that
-// follow are protected by relative margins on the large terms.
-// Straight-line code (no branch, no exec-mask region: 1 024 of these run per wave and stage set):
-//   * a subset of fewer than two pixels has a = b = c = 0 exactly, hence lam = L = 0 and lb = 0 (rcpN of an empty subset is
-//     0, a finite value);
-//   * lam slightly below zero (collinear or single-colour subsets, from the margins) is clamped to 0 ahead of the square root,
-//     so no NaN is formed and lb = 0;
-//   * for 0 <= L <= n^2 delta^2, where the bound is void, L/n - 2 delta sqrt(L) = s (s/n - 2 delta) with s = sqrt(L) <= n delta
-//     is at most -s delta: the two terms differ by a factor of two or more, far beyond any rounding, and the closing max gives 0.
-// `rcpN` = 1/n rounded toward zero (kRcpDown, cvtt_kernel_common.h): L * rcpN never exceeds L/n.
-template <bool G8 = false>
-__device__ __forceinline__ float subsetBound2D(const Sums2D &m, float rcpN, float invScaleSq, float twoDelta)
-{
-    // |sum u|, |sum v| <= 16 * 2040 fit 24 bits: v_mul_i32_i24 is a full-rate instruction, v_mul_lo_u32 is not; on the 8-bit
-    // grid the sums of squares (<= 16 * 128^2) fit as well
-    const int a = (G8 ? __mul24(m.n, m.uu) : m.n * m.uu) - __mul24(m.u, m.u);
-    const int c = (G8 ? __mul24(m.n, m.vv) : m.n * m.vv) - __mul24(m.v, m.v);
-    const int b = (G8 ? __mul24(m.n, m.uv) : m.n * m.uv) - __mul24(m.u, m.v);
-    const float fa = (float)a, fc = (float)c, fb = (float)b;
-    const float half = (fa + fc) * 0.5f;
-    const float diff = (fa - fc) * 0.5f;
-    // v_sqrt_f32 is accurate to 1 ulp; the margins below cover that
-    const float rad = __builtin_amdgcn_sqrtf(__fmaf_rn(diff, diff, fb * fb));
-    const float lam = half * 0.999998f - rad * 1.000002f; // n * scale^2 * (smaller eigenvalue), rounded down
-    const float L = fmaxf(lam, 0.0f) * invScaleSq;         // n * R
-    const float lb = (L * rcpN - twoDelta * __builtin_amdgcn_sqrtf(L)) * 0.9999f;
-    return fmaxf(lb, 0.0f);
-}
-
-} // namespace
-
-// bit k of the result = bit 4k + c of m: the partitions sub-lane c of a quad looks after
-__device__ __forceinline__ u32 everyFourth(u64 m, int c)
-{
-    u64 x = (m >> c) & 0x1111111111111111ull;
-    x = (x | (x >> 3)) & 0x0303030303030303ull;
-    x = (x | (x >> 6)) & 0x000f000f000f000full;
-    x = (x | (x >> 12)) & 0x000000ff000000ffull;
-    x = (x | (x >> 24)) & 0xffffull;
-    return (u32)x;
-}
+// The helpers of the search (they use the knobs and the PROF_* macros above): what the phases share and the single-plane
+// chains, the dual-plane search, the partition bounds.  bc7Body below is the kernel.
+#include "bc7_chain.h"
+#include "bc7_dual.h"
+#include "bc7_bounds.h"
 
 // HARD = false: the encoder.  A block whose mode-7 stage starts with at least A.hardMin partitions alive hands them to
 // the second launch (A.hardCap slots; none left: it searches them itself) and records its best without them.
@@ -2650,20 +613,9 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                 inv.rowSq[3] = (1 + sepCh) * 16;
                 inv.rowVs[3] = (13 + sepCh) * 16;
                 inv.minMax = s_raw[(5 + sepCh) * 16 + (lane >> 2)];
-                if (FAST)
-                    evalDualFast(s_P, inv, mode, indexSelector, u, numTweak, rw, rwSq, rrcpW, A.flags, T, numRefine, lane, b, bA);
-                else
-                    evalDual<FAST>(s_P, inv, mode, indexSelector, u, numTweak, rw, rwSq, rrcpW, A.flags, T, numRefine, lane, b, bA);
+                evalDual<FAST>(s_P, inv, mode, indexSelector, u, numTweak, rw, rwSq, rrcpW, A.flags, T, numRefine, lane, b, bA);
             }
 
-#ifdef CVTT_BC7_DEBUG
-            if (vBlock * 16u + (u32)(lane >> 2) == g_bc7DbgBlock && c == 0)
-            {
-                const int cfgSlot = (int)g_bc7Dbg[0];
-                g_bc7Dbg[1 + cfgSlot] = (float)(rotation * 100 + cfg);
-                g_bc7Dbg[0] = (float)(cfgSlot + 1);
-            }
-#endif
             const float combined = b.err + bA.err; // reference BC67.cpp:1942
             const int seq = 384 + cfg;
 #ifdef CVTT_BC7_PROFILE
@@ -3003,11 +955,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             // bound (subsetBoundFull) for all of them; then the sharper one (subsetBoundSharp, three times the work) for what the
             // first pass left -- on noise-like content that is little, and nothing of it goes, so a wave that sees the second
             // pass remove nothing does not run it again for modes with as many index bits.
-#ifdef CVTT_NO_SHARP_TIER2
-            const bool sharpPays = false;
-#else
             const bool sharpPays = WS_GET(WS_SHARP_NOPAY) == 0 || md.indexBits < WS_GET(WS_SHARP_NOPAY);
-#endif
             const u32 todo = aliveBits & ~tier2Done;
             const bool tier2Pays = WS_GET(WS_T2_NOPAY) == 0 || md.indexBits < WS_GET(WS_T2_NOPAY);
             const bool runPlain = tier2Pays && __ballot(todo != 0) != 0;
@@ -3137,9 +1085,6 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                     WS_SET(WS_T2_NOPAY, md.indexBits);
             }
         }
-#ifdef CVTT_BC7_PROFILE_SPLIT
-        PROF_MARK(4)
-#endif
         // nothing left for any block of the wave (the rule on RGBA noise): on to the next mode
         if (__ballot(aliveBits != 0) == 0)
             continue;
@@ -3832,11 +1777,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
 #pragma unroll
                     for (int step = 1; step < 64; step <<= 1)
                         filterCand += xorLane(filterCand, step);
-#ifdef CVTT_NO_SHARP_FILTER
-                    if (false)
-#else
                     if (WS_GET(WS_STRIKES) < CVTT_FILTER_STRIKES && filterCand >= 2 * filterNeed)
-#endif
                     {
                         bool firstRound = true;
                         for (int i = iLo + c; __ballot(i < iHi) != 0; i += 4)
@@ -4051,9 +1992,6 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
         }
     }
 
-#ifdef CVTT_BC7_PROFILE_SPLIT
-    PROF_MARK(3)
-#endif
     // ===================== fix-ups + bit packing (reference BC67.cpp:2003-2203) ==========
     REFRESH_LANE();
     {
@@ -4374,13 +2312,15 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
     }
     PROF_MARK(5)
     PROF_FLUSH
+}
 #undef REFRESH_LANE
 #undef valid
 #undef anyBlockHasAlpha
 #undef allowRGBModes
 #undef allowMode7
 #undef blockHasNonMaxAlpha
-}
+#undef WS_GET
+#undef WS_SET
 
 template <bool FAST, bool PT, bool HARD>
 // (the punch-through instantiation holds 22 KB of LDS: two waves per SIMD is all that fits, so it may use their registers)

@@ -158,7 +158,7 @@ MIX.append(("seq:2cvt_2mul_x16", ([_CVT] * 2 + [_MUL] * 2) * 16))
 MIX.append(("seq:1cvt_3mul_x16", ([_CVT] + [_MUL] * 3) * 16))
 MIX.append(("seq:4cvt_12mul_x4", ([_CVT] * 4 + [_MUL] * 12) * 4))
 MIX.append(("seq:16cvt_48mul", [_CVT] * 16 + [_MUL] * 48))
-# the pixel step of the BC7 dual-plane search (bc7_kernel.hip evalDualFast), 1.6 pixels: as compiled, and interleaved
+# the pixel step of the BC7 dual-plane search (bc7_dual.h evalDual, fast indexing), 1.6 pixels: as compiled, and interleaved
 _PIX = [_CVT] * 4 + [_SUB] * 4 + [_MUL] * 4 + [_ADD] * 3 + [_MIN, _MAX, _RND, _MIN, _MAX, _RND] + [_MUL] * 11 + [_ADD] * 7 + [_CVI] * 1
 _PIXI = [_CVT, _SUB, _MUL, _ADD, _CVT, _SUB, _MUL, _ADD, _CVT, _SUB, _MUL, _ADD, _CVT, _SUB, _MUL, _MUL, _MIN, _MUL, _MAX, _MUL, _RND, _MUL, _MIN,
          _MUL, _MAX, _MUL, _RND, _MUL, _CVI, _MUL, _ADD, _MUL, _ADD, _MUL, _ADD, _MUL, _ADD, _ADD, _ADD, _ADD]

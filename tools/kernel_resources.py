@@ -52,7 +52,7 @@ def kernels(path=None):
         except OSError:
             dem = []
         if len(dem) == len(names):
-            res = {re.sub(r"\(.*", "", d).replace("void ", ""): res[n] for d, n in zip(dem, names)}
+            res = {re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void ", ""): res[n] for d, n in zip(dem, names)}
     return res
 
 
