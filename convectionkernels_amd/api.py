@@ -199,6 +199,7 @@ _EXPORTS = (
     "cvttmi_dropin_set_devices",
     "cvttmi_format_info", "cvttmi_encode_device", "cvttmi_encode",
     "cvttmi_mip_level_count", "cvttmi_mip_layout", "cvttmi_build_mips_device",
+    "cvttmi_decode_image_device", "cvttmi_decode_mips_device",
 )
 
 _lib = None
@@ -301,6 +302,10 @@ def load_library():
     lib.cvttmi_measure_image_error_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                       ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p]
+    lib.cvttmi_decode_image_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    lib.cvttmi_decode_mips_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     lib.cvttmi_psnr.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.cvttmi_psnr.restype = ctypes.c_double
     lib.cvttmi_selftest_arith.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
@@ -923,6 +928,87 @@ class Context:
             self._check(self._lib.cvttmi_compact_rows_device(self._h, out[L.firstBlock:].data_ptr(), packed[L.firstTile:].data_ptr(),
                                                              L.width, L.height, bpb, sp), "compact_rows")
         return [out[L.firstBlock: L.firstBlock + L.blockCount] for L in layout]
+
+
+    # -- packed blocks -> linear images on the device (cvtt_mi355x.h, "decoding into images") --
+    @staticmethod
+    def _image_dtype(fmt):
+        """torch dtype of the (H, W, 4) image `fmt` decodes into"""
+        import torch
+        return torch.float16 if fmt in ("bc6hu", "bc6hs") else torch.int8 if fmt in ("bc4s", "bc5s") else torch.uint8
+
+    def _image_format(self, fmt, what):
+        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 decodes to PixelBlockScalarS16: no image form)
+            raise CvttError("%s: %r has no image form" % (what, fmt) if fmt in TEXTURE_FORMATS else "unknown format %r" % (fmt,))
+        return TEXTURE_FORMATS[fmt][:2]
+
+    def _packed_in(self, packed, nbytes, what):
+        """a CUDA tensor of this context's device holding exactly `nbytes`"""
+        import torch
+        if not (isinstance(packed, torch.Tensor) and packed.is_cuda):
+            raise CvttError("%s must be a CUDA tensor" % what)
+        if packed.device.index != self.device:
+            raise CvttError("%s lives on cuda:%d but this context was created for cuda:%d" % (what, packed.device.index, self.device))
+        if packed.numel() * packed.element_size() != nbytes:
+            raise CvttError("%s must hold exactly %d bytes, got %d" % (what, nbytes, packed.numel() * packed.element_size()))
+        return packed.contiguous()
+
+    def decode_image(self, fmt, packed, width, height, out=None, stream=None):
+        """The ceil(W/4) x ceil(H/4) packed blocks of `fmt` (a CUDA tensor: what encode_image returns and a container holds;
+        any count) -> the (H, W, 4) CUDA image: uint8, int8 for bc4s / bc5s, float16 for BC6H, texel values as decode() gives
+        them.  Every format but R11.  out: an (H, W, 4) CUDA tensor of that dtype to decode into, texels contiguous
+        (stride(2) == 1, stride(1) == 4), any row stride of at least 4 * W elements -- a window of an atlas; only the texels of
+        the image are written, and `out` is never replaced by a copy."""
+        import torch
+        fid, bpb = self._image_format(fmt, "decode_image")
+        w, h = int(width), int(height)
+        if w < 1 or h < 1:
+            raise CvttError("decode_image: a %d x %d image" % (w, h))
+        b = self._packed_in(packed, ((w + 3) // 4) * ((h + 3) // 4) * bpb, "packed (the blocks of a %dx%d %s image)" % (w, h, fmt))
+        dtype = self._image_dtype(fmt)
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=dtype, device=b.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == b.device and out.dtype == dtype
+                  and tuple(out.shape) == (h, w, 4) and out.stride(2) == 1 and out.stride(1) == 4
+                  and (h == 1 or (out.stride(0) >= 4 * w and out.stride(0) % 4 == 0)) and out.data_ptr() % (4 * out.element_size()) == 0):
+            raise CvttError("out must be a (%d, %d, 4) %s CUDA tensor on %s with contiguous texels and a row stride of whole texels, "
+                            "at least %d elements" % (h, w, str(dtype).replace("torch.", ""), b.device, 4 * w))
+        esz = out.element_size()
+        pitch = (out.stride(0) if h > 1 else 4 * w) * esz
+        self._check(self._lib.cvttmi_decode_image_device(self._h, fid, out.data_ptr(), pitch, PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8,
+                                                         b.data_ptr(), w, h, ctypes.c_void_p(self._stream(stream, b.device))),
+                    "decode_image(%s)" % fmt)
+        return out
+
+    def decode_mips(self, fmt, levels, width, height, stream=None):
+        """[packed blocks of level L] of a width x height texture (CUDA tensors: what encode_mips returns, or the levels
+        read_ktx_mips / read_dds_mips give, uploaded) -> the list of the decoded levels (cvttmi_decode_mips_device, ONE launch
+        for the chain): [0] an (H, W, 4) tensor of its own, the others (h_L, w_L, 4) views into one allocation laid out by
+        mip_layout, like build_mips.  Levels that are not already consecutive in one allocation are concatenated once."""
+        import torch
+        fid, bpb = self._image_format(fmt, "decode_mips")
+        levels = list(levels)
+        w, h = int(width), int(height)
+        if w < 1 or h < 1 or not 1 <= len(levels) <= max(w, h).bit_length():
+            raise CvttError("decode_mips: a %d x %d texture has 1 .. %d levels, got %d" % (w, h, max(w, h, 1).bit_length(), len(levels)))
+        dtype = self._image_dtype(fmt)
+        esz = 2 if dtype == torch.float16 else 1
+        layout = mip_layout(w, h, 4 * esz, bpb, len(levels))
+        levels = [self._packed_in(t, L.blockCount * bpb, "level %d (the blocks of a %dx%d %s image)" % (l, L.width, L.height, fmt))
+                  for l, (t, L) in enumerate(zip(levels, layout))]
+        base = levels[0].data_ptr()
+        if all(t.data_ptr() == base + L.packedByteOffset for t, L in zip(levels, layout)):
+            packed = levels[0]  # (already in container order, as encode_mips returns them)
+        else:
+            packed = torch.cat([t.reshape(-1).view(torch.uint8) for t in levels])
+        image = torch.empty((h, w, 4), dtype=dtype, device=packed.device)
+        pyramid = torch.empty(layout.pyramid_bytes, dtype=torch.uint8, device=packed.device)
+        self._check(self._lib.cvttmi_decode_mips_device(self._h, fid, image.data_ptr(), 4 * w * esz, pyramid.data_ptr() if len(layout) > 1 else None,
+                                                        layout.pyramid_bytes, PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8, packed.data_ptr(),
+                                                        w, h, len(layout), ctypes.c_void_p(self._stream(stream, packed.device))),
+                    "decode_mips(%s)" % fmt)
+        return [image] + [pyramid[L.byteOffset: L.byteOffset + L.rowPitchBytes * L.height].view(dtype).view(L.height, L.width, 4)
+                          for L in layout[1:]]
 
 
 _default_ctx = {}

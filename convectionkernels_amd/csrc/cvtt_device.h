@@ -153,4 +153,22 @@ struct CvttEtcArgs
     uint32_t alphaThreshold; // punch-through: pixels with alpha below this are transparent (reference ETC.cpp:1672-1675)
 };
 
+// Decoding a mip chain into linear images (cvttmi_decode_mips_device): where each level's texels go, and which packed
+// blocks of the launch are its own -- [firstBlock, next level's firstBlock), row-major, blocksPerRow = ceil(width / 4).
+// The whole table travels as a kernel argument.
+struct CvttDecodeLevel
+{
+    uint8_t *image;
+    size_t pitch; // bytes between texel rows
+    uint32_t width, height;
+    uint32_t firstBlock, blocksPerRow;
+};
+const uint32_t kCvttDecodeLevels = 32; // cvttmi_mip_level_count never returns more
+struct CvttDecodeLevels
+{
+    CvttDecodeLevel level[kCvttDecodeLevels];
+    uint32_t count;
+    uint32_t numBlocks; // of all levels
+};
+
 #endif

@@ -765,6 +765,110 @@ __global__ __launch_bounds__(256) void cvttmi_decode_kernel(const uint8_t *__res
     }
 }
 
+// ---- packed blocks -> a linear image (cvttmi_decode_image_device / cvttmi_decode_mips_device).  One lane decodes one block
+// and stores its four texel rows; the lanes of a wave hold horizontally adjacent blocks, so one store instruction of a wave
+// covers one contiguous run of an image row.  Interior blocks of an image whose base and pitch are multiples of 16 store a
+// row as 16 bytes (RGBA8) or 2 x 16 bytes (RGBA16F); a block cut by the right or bottom edge, and every block of an image
+// that is not so aligned, stores the texels inside width x height one by one.  Nothing else is written. ----
+struct DecodeTarget
+{
+    uint8_t *image;
+    size_t pitch;
+    u32 width, height;
+};
+
+// block (bx, by) of the image: bx < ceil(width / 4), by < ceil(height / 4)
+template <int F>
+__device__ __forceinline__ void storeBlockTexels(const int px[16][4], const DecodeTarget &t, u32 bx, u32 by)
+{
+    constexpr u32 kWords = Fmt<F>::hdr ? 2u : 1u; // 32-bit words of a texel
+    u32 w[16][kWords];
+#pragma unroll
+    for (int p = 0; p < 16; p++)
+    {
+        if (Fmt<F>::hdr)
+        {
+            w[p][0] = ((u32)px[p][0] & 0xffffu) | (((u32)px[p][1] & 0xffffu) << 16);
+            w[p][kWords - 1] = ((u32)px[p][2] & 0xffffu) | (((u32)px[p][3] & 0xffffu) << 16);
+        }
+        else
+            w[p][0] = ((u32)px[p][0] & 0xffu) | (((u32)px[p][1] & 0xffu) << 8) | (((u32)px[p][2] & 0xffu) << 16) | (((u32)px[p][3] & 0xffu) << 24);
+    }
+    const u32 x0 = bx * 4u, y0 = by * 4u;
+    const u32 cols = t.width - x0 < 4u ? t.width - x0 : 4u, rows = t.height - y0 < 4u ? t.height - y0 : 4u;
+    uint8_t *dst = t.image + (size_t)y0 * t.pitch + (size_t)x0 * (4u * kWords);
+    const bool wide = ((reinterpret_cast<uintptr_t>(t.image) | t.pitch) & 15u) == 0;
+    if (wide && cols == 4u && rows == 4u)
+    {
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+        {
+            uint4 *row = reinterpret_cast<uint4 *>(dst + (size_t)r * t.pitch);
+            if (Fmt<F>::hdr)
+            {
+                row[0] = make_uint4(w[4 * r][0], w[4 * r][kWords - 1], w[4 * r + 1][0], w[4 * r + 1][kWords - 1]);
+                row[1] = make_uint4(w[4 * r + 2][0], w[4 * r + 2][kWords - 1], w[4 * r + 3][0], w[4 * r + 3][kWords - 1]);
+            }
+            else
+                row[0] = make_uint4(w[4 * r][0], w[4 * r + 1][0], w[4 * r + 2][0], w[4 * r + 3][0]);
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if ((u32)r < rows && (u32)c < cols)
+            {
+                uint8_t *texel = dst + (size_t)r * t.pitch + (size_t)c * (4u * kWords);
+                if (Fmt<F>::hdr)
+                    *reinterpret_cast<uint2 *>(texel) = make_uint2(w[4 * r + c][0], w[4 * r + c][kWords - 1]);
+                else
+                    *reinterpret_cast<u32 *>(texel) = w[4 * r + c][0];
+            }
+}
+
+constexpr u32 kImageWG = 256; // lanes of a workgroup = blocks of one block row
+
+// grid: x over the block columns (kImageWG per workgroup), y and z over the block rows (y alone is limited to 65 535), so
+// no lane divides.  bc: the blocksPerRow x blockRows blocks, row-major.
+template <int F>
+__global__ __launch_bounds__(256) void cvttmi_decode_image_kernel(const uint8_t *__restrict__ bc, const DecodeTarget img, u32 blocksPerRow,
+                                                                u32 blockRows, const CvttDeviceTables *__restrict__ T)
+{
+    const u32 bx = blockIdx.x * kImageWG + threadIdx.x;
+    const u32 by = blockIdx.z * gridDim.y + blockIdx.y;
+    if (bx >= blocksPerRow || by >= blockRows)
+        return;
+    int px[16][4];
+    decodeTexels<F>(loadPacked<F>(bc, (size_t)by * blocksPerRow + bx), T, px);
+    storeBlockTexels<F>(px, img, bx, by);
+}
+
+// A whole mip chain in one launch: the levels' blocks are consecutive in bc, so a lane's global block index is also its
+// block's place in bc; its level is the last one whose firstBlock is not above that index (the table is in level order).
+template <int F>
+__global__ __launch_bounds__(256) void cvttmi_decode_mips_kernel(const uint8_t *__restrict__ bc, const CvttDecodeLevels levels,
+                                                               const CvttDeviceTables *__restrict__ T)
+{
+    const u32 block = blockIdx.x * kImageWG + threadIdx.x;
+    if (block >= levels.numBlocks)
+        return;
+    u32 l = 0;
+    for (u32 i = 1; i < levels.count; i++)
+        l = block >= levels.level[i].firstBlock ? i : l;
+    const CvttDecodeLevel &L = levels.level[l];
+    DecodeTarget img;
+    img.image = L.image;
+    img.pitch = L.pitch;
+    img.width = L.width;
+    img.height = L.height;
+    const u32 local = block - L.firstBlock, by = local / L.blocksPerRow;
+    int px[16][4];
+    decodeTexels<F>(loadPacked<F>(bc, block), T, px);
+    storeBlockTexels<F>(px, img, local - by * L.blocksPerRow, by);
+}
+
 // half bits -> float (exact)
 __device__ __forceinline__ float halfToFloat(int bits) { return __half2float(__ushort_as_half((unsigned short)(bits & 0xffff))); }
 
@@ -1026,6 +1130,24 @@ hipError_t launchDecodeFormat(const void *d_bc, void *d_out, u32 numBlocks, cons
     return hipGetLastError();
 }
 
+template <int F>
+hipError_t launchDecodeImage(const void *d_bc, const DecodeTarget &img, const CvttDeviceTables *T, hipStream_t stream)
+{
+    const u32 blocksPerRow = (u32)(((u64)img.width + 3u) / 4u), blockRows = (u32)(((u64)img.height + 3u) / 4u);
+    const u32 gy = blockRows < 65535u ? blockRows : 65535u;
+    hipLaunchKernelGGL(cvttmi_decode_image_kernel<F>, dim3((blocksPerRow + kImageWG - 1u) / kImageWG, gy, (blockRows + gy - 1u) / gy), dim3(kImageWG),
+                       0, stream, (const uint8_t *)d_bc, img, blocksPerRow, blockRows, T);
+    return hipGetLastError();
+}
+
+template <int F>
+hipError_t launchDecodeMips(const void *d_bc, const CvttDecodeLevels &levels, const CvttDeviceTables *T, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cvttmi_decode_mips_kernel<F>, dim3((u32)(((u64)levels.numBlocks + kImageWG - 1u) / kImageWG)), dim3(kImageWG), 0, stream,
+                       (const uint8_t *)d_bc, levels, T);
+    return hipGetLastError();
+}
+
 template <int F, int SRC>
 hipError_t launchMeasureFormat(const void *d_bc, const void *d_source, const MeasureImage &img, u32 numBlocks, void *d_blockError,
                                void *d_slab, cvttmi_error_totals *d_totals, int accumulate, u64 texels, const CvttDeviceTables *T,
@@ -1136,3 +1258,46 @@ extern "C" hipError_t cvttmi_launch_measure(const void *d_bc, const void *d_sour
 #undef CVTTMI_MEASURE_CASE
     return hipErrorInvalidValue;
 }
+
+// Packed blocks -> linear images: every format but R11, which has no image form (the shim rejects it, and the wrong texel
+// size for a format, before it comes here).
+#define CVTTMI_IMAGE_FORMATS(CASE) \
+    CASE(kBC7) CASE(kBC1) CASE(kBC6HU) CASE(kBC6HS) CASE(kETC2) CASE(kETC2RGBA) CASE(kBC2) CASE(kBC3) CASE(kBC4U) CASE(kBC4S) \
+    CASE(kBC5U) CASE(kBC5S) CASE(kETC1) CASE(kETC2PT) CASE(kEAC)
+
+// d_bc: the ceil(width / 4) x ceil(height / 4) blocks, row-major (fewer than 2^32); d_image: width x height texels of 4 bytes
+// (BC6H: 8), `pitch` bytes between rows
+extern "C" hipError_t cvttmi_launch_decode_image(const void *d_bc, void *d_image, size_t pitch, uint32_t width, uint32_t height, int format,
+                                                 const CvttDeviceTables *d_tables, hipStream_t stream)
+{
+    DecodeTarget img;
+    img.image = (uint8_t *)d_image;
+    img.pitch = pitch;
+    img.width = width;
+    img.height = height;
+#define CVTTMI_DECODE_IMAGE_CASE(F) \
+    case F: return launchDecodeImage<F>(d_bc, img, d_tables, stream);
+    switch (format)
+    {
+        CVTTMI_IMAGE_FORMATS(CVTTMI_DECODE_IMAGE_CASE)
+    }
+#undef CVTTMI_DECODE_IMAGE_CASE
+    return hipErrorInvalidValue;
+}
+
+// levels->level[0 .. count - 1] in level order, their blocks consecutive in d_bc; 0 < numBlocks < 2^32
+extern "C" hipError_t cvttmi_launch_decode_mips(const void *d_bc, const CvttDecodeLevels *levels, int format, const CvttDeviceTables *d_tables,
+                                                hipStream_t stream)
+{
+    if (levels->count == 0 || levels->count > kCvttDecodeLevels || levels->numBlocks == 0)
+        return hipErrorInvalidValue;
+#define CVTTMI_DECODE_MIPS_CASE(F) \
+    case F: return launchDecodeMips<F>(d_bc, *levels, d_tables, stream);
+    switch (format)
+    {
+        CVTTMI_IMAGE_FORMATS(CVTTMI_DECODE_MIPS_CASE)
+    }
+#undef CVTTMI_DECODE_MIPS_CASE
+    return hipErrorInvalidValue;
+}
+#undef CVTTMI_IMAGE_FORMATS

@@ -445,6 +445,34 @@ int cvttmi_measure_image_error_device(cvttmi_context *ctx, int format, const voi
  * R11U 2047, R11S 2046); +inf on zero error; NaN for BC6H, for channels the format does not store and for no texels. */
 double cvttmi_psnr(const cvttmi_error_totals *t, uint32_t channelMask);
 
+/* ---- decoding into images: packed blocks as a container holds them -> linear images in HBM (not part of the reference's
+ * API; the reverse of tiling, encoding and compacting rows) ----
+ * d_bc: the ceil(W/4) x ceil(H/4) blocks, row-major -- any count, it need not be a multiple of 8: what encode_image,
+ * cvttmi_compact_rows_device and the containers hold.  d_image: width x height texels, rowPitchBytes between rows.
+ * pixels: CVTTMI_PIXELS_RGBA16F for BC6HU / BC6HS and CVTTMI_PIXELS_RGBA8 for every other format; R11U / R11S have no image
+ * form.  A texel holds exactly what cvttmi_decode_device writes for it (the table under "every format"): uint8 RGBA;
+ * BC4S / BC5S int8 (r,0,0,127) / (r,g,0,127); BC6H four half bit patterns, alpha 0x3C00.
+ * cvttmi_decode_mips_device: d_bc holds the blocks of `levels` levels consecutively, as cvttmi_mip_layout(width, height, pixels,
+ * bytes per block, levels) places them (packedByteOffset) -- what the mip containers store.  Level 0 goes to d_image
+ * (rowPitchBytes between rows), levels 1 .. levels-1 into d_pyramid at the layout's byteOffset / rowPitchBytes: the mirror of
+ * cvttmi_build_mips_device.  levels == 1 needs no pyramid (d_pyramid may then be NULL).  The whole chain is ONE launch.
+ * Buffers.  The calls write exactly the texels of the image (images): never a byte before or behind them, between the end of
+ * a row and the next pitch, or in the gaps that align a level's start, whatever the edge blocks hold beyond width x height.
+ * d_image / d_pyramid: aligned to the texel (4 / 8 bytes); rowPitchBytes a multiple of the texel and at least one row; d_bc:
+ * min(bytes per block, 16).  Where an image's first texel and its pitch are both multiples of 16 bytes (per level, for a
+ * chain: the small levels have 4- or 8-byte pitches), the rows of every block that lies wholly inside the image are stored 16
+ * bytes at a time; blocks cut by the right or bottom edge, and every block of an image that is not so aligned, texel by texel.
+ * CVTTMI_E_INVALID before anything is queued, nothing written: NULL pointers, a zero size, an unknown format id or R11, a
+ * pixel kind that is not the format's (CVTTMI_PIXELS_RGBA8_SNORM included), rowPitchBytes below the row or no multiple of the
+ * texel, a misaligned pointer, levels 0 or above cvttmi_mip_level_count, pyramidBytes below the layout's, 2^32 blocks or more.
+ * Both calls are simply queued on the stream given (no context work space); images, pyramid and blocks must not overlap.
+ * Device pointers only. */
+int cvttmi_decode_image_device(cvttmi_context *ctx, int format, void *d_image, size_t rowPitchBytes, int pixels,
+                               const void *d_bc, uint32_t width, uint32_t height, void *hipStream);
+int cvttmi_decode_mips_device(cvttmi_context *ctx, int format, void *d_image, size_t rowPitchBytes,
+                              void *d_pyramid, size_t pyramidBytes, int pixels, const void *d_bc,
+                              uint32_t width, uint32_t height, uint32_t levels, void *hipStream);
+
 /* ---- one job on several devices (csrc/multi.cpp).  The north-star's "large images shard by block row across the GPUs of one
  * node", for callers of this C interface (the reference has no counterpart: its callers parallelise by threads over groups,
  * etc2packer.cpp:215-281).  Groups of 8 blocks are independent, so the search needs no exchange: the job is cut into
