@@ -254,8 +254,15 @@ __device__ __forceinline__ void topEigenvector(const float (&M)[10], float (&e)[
 // (lp: the block's sixteen pixels in LDS.  They are read twice, for the sums and for the projections, rather than kept in
 // registers in between: this function is the register peak of the bounds.)
 template <int N>
-__device__ __forceinline__ float subsetBoundSharp(const u32 *lp, u32 mask, const float (&w)[4], float delta, float wSq, bool fourLevels)
+__device__ __forceinline__ float subsetBoundSharp(const u32 *lp, u32 mask, const float (&w)[4], float delta, float wSq, bool fourLevels
+#ifdef CVTT_BC7_BOUND_DUMP
+                                                  , float (&dUsed)[4] // the bound dump: the direction d (zeros when the plain bound is all there is)
+#endif
+)
 {
+#ifdef CVTT_BC7_BOUND_DUMP
+    dUsed[0] = dUsed[1] = dUsed[2] = dUsed[3] = 0.0f;
+#endif
     RawSums r;
     {
         asm volatile("" : "+v"(lp));
@@ -301,6 +308,11 @@ __device__ __forceinline__ float subsetBoundSharp(const u32 *lp, u32 mask, const
             M[i] = (N == 4 || i < 6) ? m.cov[i < N * (N + 1) / 2 ? i : 0] : 0.0f;
         topEigenvector(M, e);
     }
+#ifdef CVTT_BC7_BOUND_DUMP
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        dUsed[i] = (i < N) ? e[i] : 0.0f;
+#endif
     float L = 0.0f, Sd[N];
 #pragma unroll
     for (int a = 0; a < N; a++)

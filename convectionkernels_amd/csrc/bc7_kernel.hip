@@ -153,6 +153,70 @@ extern "C" int cvttmi_bc7_prof_read(unsigned long long *out)
 #define PROF_STAGE_LANES(stage, slot, pred)
 #endif
 
+// Developer-only bound dump (-DCVTT_BC7_BOUND_DUMP, lib/variants/libcvtt_mi355x_bounddump.so): every value the search compares
+// with a block's best error in order to drop a candidate is appended to a device buffer as one 48-byte record, where it is
+// formed and where it is read back and compared (tests/test_bc7_bound_soundness.py holds each one to the exact bound in
+// float64 and to the error the reference reaches for the candidate).  Twelve words per record:
+//   0  block index
+//   1  tier | kind << 8 | (second launch) << 16
+//        tier: 0 whole block (mode 6), 1 rotation (modes 4 / 5), 2 first tier, 3 second tier plain (subsetBoundFull),
+//              4 second tier sharp (subsetBoundSharp), 5 probe + plain bound of the rest, 6 probe + sharp bound of the rest,
+//              7 the block's final error
+//        kind: 0 formed (and stored), 1 formed, stored and compared, 2 read back from the table and compared,
+//              3 one subset's share of a sharp bound (words 8..11: the direction d it used), 4 final error
+//   2  bound set | mode << 8 | subsets << 16 | index bits the value holds for << 24  (4 = any mode of the set)
+//   3  partition or rotation | subset << 8
+//   4  the value as computed      5  the value as the table gives it back (fabs of the upper 16 bits; the value itself where
+//   6  the best error compared with   7  1 = dropped                                                    it is kept in a register)
+//   8..11  per site: the static alpha error, the probed subset's error and the bound of the rest, d, ...
+// The counter advances with an ordinary atomicAdd; records past the capacity are counted and not written.
+#ifdef CVTT_BC7_BOUND_DUMP
+__device__ u32 *g_bc7BoundBuf;
+__device__ u32 g_bc7BoundCap;
+__device__ u32 g_bc7BoundCount;
+extern "C" int cvttmi_bc7_bound_dump_set(void *deviceBuffer, uint32_t capacityRecords)
+{
+    const uint32_t zero = 0;
+    u32 *buf = static_cast<u32 *>(deviceBuffer);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7BoundBuf), &buf, sizeof(buf)) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7BoundCap), &capacityRecords, sizeof(capacityRecords)) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7BoundCount), &zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+extern "C" int cvttmi_bc7_bound_dump_count(uint32_t *out)
+{
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bc7BoundCount), sizeof(*out)) == hipSuccess ? 0 : -1;
+}
+enum : u32 { BD_WHOLE6 = 0, BD_ROT = 1, BD_TIER1 = 2, BD_FULL = 3, BD_SHARP = 4, BD_PROBE_FULL = 5, BD_PROBE_SHARP = 6, BD_FINAL = 7 };
+enum : u32 { BD_FORM = 0, BD_FORM_CMP = 1, BD_RELOAD = 2, BD_SUBSET = 3, BD_END = 4 };
+__device__ __noinline__ void boundDumpEmit(u32 block, u32 w1, u32 w2, u32 w3, float computed, float stored, float err, u32 dropped,
+                                           float x0, float x1, float x2, float x3)
+{
+    u32 *const buf = g_bc7BoundBuf;
+    if (buf == nullptr)
+        return;
+    const u32 at = atomicAdd(&g_bc7BoundCount, 1u);
+    if (at >= g_bc7BoundCap)
+        return;
+    u32 *r = buf + (size_t)at * 12u;
+    r[0] = block;
+    r[1] = w1;
+    r[2] = w2;
+    r[3] = w3;
+    r[4] = __builtin_bit_cast(u32, computed);
+    r[5] = __builtin_bit_cast(u32, stored);
+    r[6] = __builtin_bit_cast(u32, err);
+    r[7] = dropped;
+    r[8] = __builtin_bit_cast(u32, x0);
+    r[9] = __builtin_bit_cast(u32, x1);
+    r[10] = __builtin_bit_cast(u32, x2);
+    r[11] = __builtin_bit_cast(u32, x3);
+}
+#define BOUND_DUMP(...) do { __VA_ARGS__; } while (0)
+#else
+#define BOUND_DUMP(...)
+#endif
+
 // The helpers of the search (they use the knobs and the PROF_* macros above): what the phases share and the single-plane
 // chains, the dual-plane search, the partition bounds.  bc7Body below is the kernel.
 #include "bc7_chain.h"
@@ -248,6 +312,13 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
     }
     const u32 blockIndex = (HARD ? (hardBlock & ~15u) : vBlock * 16u) + (u32)(lane >> 2);
     const bool inRange = blockIndex < A.numBlocks;
+#ifdef CVTT_BC7_BOUND_DUMP
+    auto bdEmit = [&](u32 tier, u32 kind, u32 set, u32 mode, u32 numSub, u32 bits, u32 part, u32 sub, float computed, float stored, float err,
+                      bool dropped, float x0 = 0.0f, float x1 = 0.0f, float x2 = 0.0f, float x3 = 0.0f) {
+        boundDumpEmit(blockIndex, tier | (kind << 8) | (HARD ? 1u << 16 : 0u), set | (mode << 8) | (numSub << 16) | (bits << 24), part | (sub << 8),
+                      computed, stored, err, dropped ? 1u : 0u, x0, x1, x2, x3);
+    };
+#endif
     // The per-lane predicates of the search live as bits of one register (`lf`) rather than as one lane mask each: the
     // scalar registers a mask takes (two each, for the whole kernel) are what the register allocator runs out of first.
     enum : u32 { LF_VALID = 1u, LF_ANY_ALPHA = 2u, LF_ALLOW_RGB = 4u, LF_ALLOW_M7 = 8u, LF_NONMAX_ALPHA = 16u };
@@ -375,6 +446,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             // mode 6 is the first single-plane stage: its bound waits where that stage looks for it
             if (c == 0)
                 lbStore(0, lane >> 2, lbMode6);
+            BOUND_DUMP(if (c == 0 && valid) bdEmit(BD_WHOLE6, BD_FORM, 3, 6, 1, 4, 0, 0, lbMode6, lbLoad(0, lane >> 2), work.err, false));
         }
         // rotation r codes channel r-1 (alpha for r = 0) on its own; the other three share a line
         if (!HARD)
@@ -396,6 +468,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             m.cov[5] = pick(tri(2, 2), tri(3, 3), tri(3, 3), tri(3, 3)); // (c', c')
 #undef pick
             lbRotMine = shapeErrorLowerBound<3>(m, 16.0f, c == 0 ? d0 : c == 1 ? d1 : c == 2 ? d2 : d3);
+            BOUND_DUMP(if (valid) bdEmit(BD_ROT, BD_FORM, 3, 4, 1, 4, (u32)c, 0, lbRotMine, lbRotMine, work.err, false, c == 0 ? d0 : c == 1 ? d1 : c == 2 ? d2 : d3));
         }
         // search the rotations in the order of their bounds summed over the wave: the likely
         // winner first, so that the others meet a tight best error
@@ -546,6 +619,9 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             {
                 // the second plane costs >= 0, the first at least the bound of its three channels
                 const float lb = lbRotOf(rotation);
+                // (word 8: 1 = the whole wave skipped the step; a block whose bound exceeds its best is searched along with the others otherwise)
+                BOUND_DUMP(if (valid && c == 0) bdEmit(BD_ROT, BD_RELOAD, 3, (u32)mode, 1, (u32)indexSelector, (u32)rotation, 0, lb, lb, work.err, lb > work.err,
+                                                       __ballot(valid && !(lb > work.err)) == 0 ? 1.0f : 0.0f));
                 if (__ballot(valid && !(lb > work.err)) == 0)
                     continue;
             }
@@ -905,6 +981,8 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                         }
                         lb += staticErr; // (lb >= +0: adding 0.0f changes nothing)
                         lbStore(partition, blk, lb);
+                        BOUND_DUMP(if (valid) bdEmit(BD_TIER1, BD_FORM_CMP, (u32)boundSet, (u32)mode, (u32)numSubsets, 4, (u32)partition, 0, lb, lbLoad(partition, blk),
+                                                     work.err, lb > work.err, staticErr));
                         freshAlive |= (lb > work.err) ? 0u : (1u << k);
                         selA = selA1;
                         selB = selB1;
@@ -941,6 +1019,10 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                 for (int k = 0; k * 4 < numPartitions; k++)
                 {
                     const float raw = lbLoadRaw(4 * k + c, blk);
+                    // (the tier of a marked entry: the sharper pass has been over the set iff WS_SHARP_RAN says so)
+                    BOUND_DUMP(if ((aliveBits >> k) & 1u) bdEmit(boundSet == 3 ? BD_WHOLE6 : (__builtin_bit_cast(u32, raw) >> 31) ? (WS_GET(WS_SHARP_RAN) < 4 ? BD_SHARP : BD_FULL) : BD_TIER1,
+                                                                 BD_RELOAD, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)(4 * k + c), 0,
+                                                                 __builtin_fabsf(raw), __builtin_fabsf(raw), work.err, __builtin_fabsf(raw) > work.err, (float)WS_GET(WS_BOUND_BITS)));
                     if (__builtin_fabsf(raw) > work.err)
                         aliveBits &= ~(1u << k);
                     tier2Done |= (__builtin_bit_cast(u32, raw) >> 31) << k;
@@ -1017,6 +1099,8 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                             if (!use4)
                                 lb += s_static[blk];
                             lbStoreTier2(partition, blk, fmaxf(lb, lbLoad(partition, blk)));
+                            BOUND_DUMP(bdEmit(BD_FULL, BD_FORM_CMP, (u32)boundSet, (u32)mode, (u32)numSubsets, 4, (u32)partition, 0, lb, lbLoad(partition, blk), work.err,
+                                              lb > work.err, use4 ? 0.0f : s_static[blk]));
                             if (lb > work.err)
                                 aliveBits &= ~(1u << k);
                         }
@@ -1052,11 +1136,21 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                             for (int sub = 0; sub < numSubsets; sub++)
                             {
                                 const u32 sm = subsetMaskOf(numSubsets, partition, sub);
+#ifdef CVTT_BC7_BOUND_DUMP
+                                float dUsed[4];
+                                const float part1 = use4 ? subsetBoundSharp<4>(&s_pix[blk][0], sm, lw, A.delta4, wSq4, fourLevels, dUsed) : subsetBoundSharp<3>(&s_pix[blk][0], sm, lw, A.delta3, wSq3, fourLevels, dUsed);
+                                bdEmit(BD_SHARP, BD_SUBSET, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)partition, (u32)sub, part1, part1, work.err, false,
+                                       dUsed[0], dUsed[1], dUsed[2], dUsed[3]);
+                                lb += part1;
+#else
                                 lb += use4 ? subsetBoundSharp<4>(&s_pix[blk][0], sm, lw, A.delta4, wSq4, fourLevels) : subsetBoundSharp<3>(&s_pix[blk][0], sm, lw, A.delta3, wSq3, fourLevels);
+#endif
                             }
                             if (!use4)
                                 lb += s_static[blk];
                             lbStoreTier2(partition, blk, fmaxf(lb, lbLoad(partition, blk)));
+                            BOUND_DUMP(bdEmit(BD_SHARP, BD_FORM_CMP, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)partition, 0, lb, lbLoad(partition, blk),
+                                              work.err, lb > work.err, use4 ? 0.0f : s_static[blk]));
                             if (lb > work.err)
                             {
                                 aliveBits &= ~(1u << k);
@@ -1242,6 +1336,14 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                     }
                 }
                 bool offer = pick < 64 && !(pickLb > work.err);
+#ifdef CVTT_BC7_BOUND_DUMP
+                if (prune && pick < 64 && (pick & 3) == c)
+                {
+                    const float raw = lbLoadRaw(pick, blk);
+                    bdEmit(boundSet == 3 ? BD_WHOLE6 : (__builtin_bit_cast(u32, raw) >> 31) ? (WS_GET(WS_SHARP_RAN) < 4 ? BD_SHARP : BD_FULL) : BD_TIER1, BD_RELOAD,
+                           (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)pick, 0, pickLb, pickLb, work.err, pickLb > work.err, (float)WS_GET(WS_BOUND_BITS), 1.0f);
+                }
+#endif
                 if (!offer)
                     aliveBits = 0; // everything left costs even more
                 if (ptStage)
@@ -1761,7 +1863,8 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                                     lbRest += use4 ? subsetBoundFull<4>(rs, lwf, A.delta4) : subsetBoundFull<3>(rs, lwf, A.delta3);
                                 }
                                 const float lbTotal = (eProbed + lbRest) * 0.9999995f;
-
+                                BOUND_DUMP(bdEmit(BD_PROBE_FULL, BD_FORM_CMP, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)partition, (u32)ps, lbTotal, lbTotal,
+                                                  work.err, lbTotal > work.err, eProbed, lbRest));
                                 if (!(lbTotal > work.err))
                                     surv |= 1ull << partition;
                             }
@@ -1795,10 +1898,21 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                                     if (sub == ps)
                                         continue;
                                     const u32 sm = subsetMaskOf(numSubsets, partition, sub);
+#ifdef CVTT_BC7_BOUND_DUMP
+                                    float dUsed[4];
+                                    const float part1 = use4 ? subsetBoundSharp<4>(&s_pix[blk][0], sm, lwf, A.delta4, A.wSqSum3 + A.wSq[3], md.indexBits == 2, dUsed)
+                                                             : subsetBoundSharp<3>(&s_pix[blk][0], sm, lwf, A.delta3, A.wSqSum3, md.indexBits == 2, dUsed);
+                                    bdEmit(BD_PROBE_SHARP, BD_SUBSET, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)partition, (u32)sub, part1, part1, work.err, false,
+                                           dUsed[0], dUsed[1], dUsed[2], dUsed[3]);
+                                    lbRest += part1;
+#else
                                     lbRest += use4 ? subsetBoundSharp<4>(&s_pix[blk][0], sm, lwf, A.delta4, A.wSqSum3 + A.wSq[3], md.indexBits == 2)
                                                    : subsetBoundSharp<3>(&s_pix[blk][0], sm, lwf, A.delta3, A.wSqSum3, md.indexBits == 2);
+#endif
                                 }
                                 const float lbTotal = (eProbed + lbRest) * 0.9999995f;
+                                BOUND_DUMP(bdEmit(BD_PROBE_SHARP, BD_FORM_CMP, (u32)boundSet, (u32)mode, (u32)numSubsets, (u32)md.indexBits, (u32)partition, (u32)ps, lbTotal, lbTotal,
+                                                  work.err, lbTotal > work.err, eProbed, lbRest));
                                 if (lbTotal > work.err)
                                 {
                                     surv &= ~(1ull << partition);
@@ -2285,6 +2399,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                 cand.packed[3] = w3;
                 cand.err = improved ? work.err : FLT_MAX;
                 cand.seq = workSeq;
+                BOUND_DUMP(bdEmit(BD_FINAL, BD_END, 0, 7, 2, 0, 0, 0, work.err, work.err, work.err, false, (float)workSeq));
                 cand.pad[0] = cand.pad[1] = 0;
                 A.hardCand[vBlock] = cand;
             }
@@ -2297,6 +2412,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             o.z = w2;
             o.w = w3;
             *reinterpret_cast<uint4 *>(out + (size_t)blockIndex * 16u) = o;
+            BOUND_DUMP(bdEmit(BD_FINAL, BD_END, 0, 0, 0, 0, 0, 0, work.err, work.err, work.err, false, (float)workSeq));
             if (!PT && A.hardCap != 0)
             {
                 const u32 slot = s_blkFlags[blk] >> 8;

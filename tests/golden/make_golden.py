@@ -9,6 +9,8 @@ Outputs (data only -- inputs, expected outputs, the generating host's RCPPS tabl
     tests/golden/config_hashes.json SHA-256 of whole-image outputs for the BASELINE configs
     tests/golden/mode_census.npz    the directed cases of tests/census_cases.py (every mode / partition / layout);
                                     `--only-mode-census` writes this file alone
+    tests/golden/bc7_single_candidate.npz  every single-candidate BC7 plan of tests/bc7_bound_ref.py on 64 blocks;
+                                    `--only-bc7-single-candidate` writes this file alone
 """
 import hashlib
 import json
@@ -81,14 +83,48 @@ def mode_census(ref, fast, rcp):
     np.savez_compressed(os.path.join(HERE, "mode_census.npz"), **arrays)
 
 
+def bc7_single_candidate(ref, fast, rcp):
+    """tests/golden/bc7_single_candidate.npz: the reference's bytes for every single-candidate plan of
+    tests/bc7_bound_ref.py (285: every partition of modes 0-3 and 7, mode 6, every rotation and index selector of modes
+    4 / 5) under default Options, on 64 blocks = eight groups of the content of tests/test_bc7_bound_soundness.py: the first
+    group of five content families, the opaque half of a sixth, and a group with alpha and a mixed group of the collinear /
+    single-colour subset blocks"""
+    import bc7_bound_ref as R
+    import test_bc7_bound_soundness as S
+    from convectionkernels_amd import api
+    groups = (0, 2, 4, 8, 11, 14, 16, 46)
+    blocks = np.concatenate([S.content_blocks()[8 * g:8 * g + 8] for g in groups])
+    ob = R._bytes(api.Options())
+    cands = R.candidates()
+    allowed = R.rgb_modes_allowed(blocks)
+    assert 16 <= allowed.sum() <= 48
+    packed = np.zeros((len(cands), len(blocks), 16), np.uint8)
+    for i, (mode, which) in enumerate(cands):
+        pb = R._bytes(R.single_candidate_plan(mode, which))
+        packed[i] = ref.encode_bc7(blocks, ob, pb)
+        # a block whose group does not allow modes 0-3 commits nothing under such a plan, and its bytes are whatever the
+        # encoder's memory held: they are left out (zeros here, not compared by the test)
+        if mode < 4:
+            packed[i][~allowed] = 0
+        cls = allowed if mode < 4 else np.ones(len(blocks), bool)
+        assert R.emitted_as_asked(packed[i], mode, which)[cls].all(), (mode, which)
+        assert (packed[i][cls] == fast.encode_bc7(blocks, ob, pb)[cls]).all(), (mode, which)  # BC7 is build-stable
+    np.savez_compressed(os.path.join(HERE, "bc7_single_candidate.npz"), blocks=blocks, rcp=rcp, groups=np.array(groups),
+                        candidates=np.array(cands, np.int32), packed=packed)
+
+
 def main():
     ref = pyref.RefLib()
     fast = pyref.RefLib(fast=True)
     rcp = ref.probe_rcp()
 
+    if "--only-bc7-single-candidate" in sys.argv:
+        bc7_single_candidate(ref, fast, rcp)
+        return
     mode_census(ref, fast, rcp)
     if "--only-mode-census" in sys.argv:
         return
+    bc7_single_candidate(ref, fast, rcp)
 
     # ---- mixed content x variants ----
     blocks = content.mixed_ldr_blocks(20260929, 24)

@@ -6,62 +6,13 @@ perturbed one (the bound must hold for any unit vector).  CPU only; the kernel's
 parity tests on the GPU (a bound that is too high there shows up as a block that differs from the reference)."""
 import numpy as np
 
+from bc7_bound_ref import W_DEFAULT as W  # default channel weights
+from bc7_bound_ref import kmeans_1d, sharp_bound  # (shared with tests/test_bc7_bound_soundness.py, which holds the kernel's values to it)
 from convectionkernels_amd import synth
 
-W = np.array([np.float32(0.2125) / np.float32(0.7154), 1.0, np.float32(0.0721) / np.float32(0.7154)], np.float64)  # default channel weights
-W2 = float((W ** 2).sum())
-DELTA = 0.5 * np.sqrt(W2)
-BETAS = [0, 0.01, 0.02, 0.03, 0.04, 0.055, 0.07, 0.085, 0.1, 0.125, 0.15, 0.175, 0.2, 0.25, 0.3, 0.375, 0.45, 0.55, 0.7, 0.85, 1.0]
 WEIGHTS = {4: [0, 21, 43, 64], 8: [0, 9, 18, 27, 37, 46, 55, 64]}
 PARTITIONS2 = [0xcccc, 0x8888, 0xeeee, 0xecc8, 0xc880, 0xfeec, 0xfec8, 0xec80, 0xc800, 0xffec, 0xfe80, 0xe800, 0xffe8, 0xff00, 0xfff0, 0xf000,
                0xf710, 0x008e, 0x7100, 0x08ce, 0x008c, 0x7310, 0x3100, 0x8cce, 0x088c, 0x3110, 0x6666, 0x366c, 0x17e8, 0x0ff0, 0x718e, 0x399c]
-
-
-def slack(x, s, n):
-    """error >= x - 2 s sqrt(n x) when every reconstructed colour is within s of the trial's line (clamped, monotone in x)"""
-    return x - 2 * s * np.sqrt(n * x) if x > 4 * n * s * s else 0.0
-
-
-def kmeans_1d(t, k):
-    """exact cost of the best clustering of t into k groups (the kernel's dynamic programme)"""
-    t = np.sort(t)
-    n = len(t)
-    if n <= k:
-        return 0.0
-    p1 = np.concatenate([[0.0], np.cumsum(t)])
-    p2 = np.concatenate([[0.0], np.cumsum(t * t)])
-    cost = lambda i, j: (p2[j] - p2[i]) - (p1[j] - p1[i]) ** 2 / (j - i)
-    d = [cost(0, j) if j else 0.0 for j in range(n + 1)]
-    for _ in range(k - 1):
-        d = [min([d[j]] + [d[i] + cost(i, j) for i in range(j)]) for j in range(n + 1)]
-    return max(d[n], 0.0)
-
-
-def sharp_bound(points_w, d, levels):
-    """subsetBoundSharp without its float margins: points_w = weighted pixels (n, 3), d = any unit vector"""
-    n = len(points_w)
-    c = points_w - points_w.mean(0)
-    S = c.T @ c
-    T = np.trace(S)
-    r_true = T - np.linalg.eigvalsh(S)[-1]
-    L = d @ S @ d
-    Rd = T - L
-    rho = np.linalg.norm(S @ d - L * d)
-    a = np.abs(d) * W
-    md = max(0.0, 2 * a.max() - a.sum())
-    perp = np.sqrt(max(W2 - md * md, 0.0))
-    sq = np.sqrt(kmeans_1d(c @ d, levels)) if levels == 4 else 0.0  # the kernel computes Q_d for the two-bit modes only
-    best = None
-    for b0, b1 in zip(BETAS[:-1], BETAS[1:]):
-        a1 = np.sqrt(1 - b1 * b1)
-        cross = 0.5 if b0 <= np.sqrt(0.5) <= b1 else max(b0 * np.sqrt(1 - b0 * b0), b1 * a1)
-        base = min((1 - b0 * b0) * Rd + b0 * b0 * L, (1 - b1 * b1) * Rd + b1 * b1 * L) - 2 * cross * rho
-        base = max(base, r_true)
-        g = base + max(0.0, a1 * sq - b1 * np.sqrt(max(Rd, 0.0))) ** 2
-        inner = max(0.0, a1 * md - b1 * perp)
-        v = slack(g, 0.5 * np.sqrt(max(W2 - inner * inner, 0.0)), n)
-        best = v if best is None else min(best, v)
-    return max(slack(r_true, DELTA, n), best)
 
 
 def error_of(q, e0, e1, levels):
