@@ -200,6 +200,7 @@ _EXPORTS = (
     "cvttmi_format_info", "cvttmi_encode_device", "cvttmi_encode",
     "cvttmi_mip_level_count", "cvttmi_mip_layout", "cvttmi_build_mips_device",
     "cvttmi_decode_image_device", "cvttmi_decode_mips_device",
+    "cvttmi_build_mips_filtered_device", "cvttmi_srgb_tables",
 )
 
 _lib = None
@@ -289,6 +290,10 @@ def load_library():
     lib.cvttmi_mip_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     lib.cvttmi_build_mips_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                                              ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]
+    lib.cvttmi_build_mips_filtered_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                      ctypes.c_void_p]
+    lib.cvttmi_srgb_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.cvttmi_decode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
@@ -359,6 +364,33 @@ TEXTURE_FORMATS = {
 
 # pixel kinds (include/cvtt_mi355x.h CVTTMI_PIXELS_*); the SNORM kind exists for the mip filter alone
 PIXELS_RGBA8, PIXELS_RGBA16F, PIXELS_RGBA8_SNORM = 0, 1, 2
+
+# mip filters (include/cvtt_mi355x.h CVTTMI_MIP_FILTER_*) and the names build_mips / encode_mips take for them
+MIP_FILTER_BOX, MIP_FILTER_SRGB, MIP_FILTER_NORMAL, MIP_FILTER_ALPHA_WEIGHTED = 0, 1, 2, 0x100
+MIP_FILTERS = {"box": MIP_FILTER_BOX, "srgb": MIP_FILTER_SRGB, "normal": MIP_FILTER_NORMAL,
+               "box+alpha": MIP_FILTER_BOX | MIP_FILTER_ALPHA_WEIGHTED, "srgb+alpha": MIP_FILTER_SRGB | MIP_FILTER_ALPHA_WEIGHTED}
+
+
+def mip_filter_value(filter):
+    """a filter name of MIP_FILTERS, or a MIP_FILTER_* value (flag included) -> the value the library takes"""
+    if isinstance(filter, str):
+        if filter not in MIP_FILTERS:
+            raise CvttError("unknown mip filter %r (one of %s)" % (filter, ", ".join(MIP_FILTERS)))
+        return MIP_FILTERS[filter]
+    if isinstance(filter, bool) or not isinstance(filter, int) or not 0 <= filter <= 0xFFFFFFFF:
+        raise CvttError("mip filter must be a name or a MIP_FILTER_* value, got %r" % (filter,))
+    return filter
+
+
+def srgb_tables():
+    """cvttmi_srgb_tables: (T, U) of the sRGB mip filter -- T[v], v = 0..255, uint16 linear light of a byte; U[k - 1], k = 1..255,
+    uint32, the smallest sum of four T that encodes to k or more"""
+    import numpy as np
+    t, u = np.zeros(256, np.uint16), np.zeros(255, np.uint32)
+    rc = load_library().cvttmi_srgb_tables(t.ctypes.data, u.ctypes.data)
+    if rc != 0:
+        raise CvttError("cvttmi_srgb_tables failed (%d)" % rc)
+    return t, u
 
 
 class MipLevel(ctypes.Structure):
@@ -881,13 +913,16 @@ class Context:
             raise CvttError("image must be RGBA8 or RGBA16F")
         return image if image.stride(2) == 1 and image.stride(1) == 4 else image.contiguous()
 
-    # -- mip chains: 2x2 box filter on the device, and the whole chain through one encode call --
-    def build_mips(self, image, levels=None, signed=False, stream=None):
+    # -- mip chains: 2x2 filter on the device, and the whole chain through one encode call --
+    def build_mips(self, image, levels=None, signed=False, stream=None, filter="box"):
         """(H,W,4) CUDA image -> the list of its mip levels (cvttmi_build_mips_device): [0] is the image itself, the others are
         (h_L, w_L, 4) views of the image's dtype into ONE allocation laid out by mip_layout.  Level L+1 is max(1, w_L >> 1) x
         max(1, h_L >> 1), a 2x2 box of the rounded level L (an odd last row / column is dropped).  uint8: (a+b+c+d+2) >> 2;
         int8, or signed=True (the bytes BC4S / BC5S read): the same on int8 with an arithmetic shift; a 2-byte dtype: RGBA16F,
-        ((a+b)+(c+d)) * 0.25 in float, rounded to nearest even.  levels: None = the full chain down to 1x1."""
+        ((a+b)+(c+d)) * 0.25 in float, rounded to nearest even.  levels: None = the full chain down to 1x1.
+        filter (cvttmi_build_mips_filtered_device; a name or a MIP_FILTER_* value): "box" is the rule above; "srgb" averages the
+        colour channels of a uint8 image in linear light; "box+alpha" / "srgb+alpha" weight them by the texels' alphas; "normal"
+        renormalises the summed vectors of a uint8 or int8 normal map.  Alpha always takes the box rule."""
         import torch
         image = self._image_in(image)
         h, w = int(image.shape[0]), int(image.shape[1])
@@ -898,22 +933,24 @@ class Context:
         layout = mip_layout(w, h, 4 * esz, 16, levels)
         pyramid = torch.empty(layout.pyramid_bytes, dtype=torch.uint8, device=image.device)
         stream = self._stream(stream, image.device)
-        self._check(self._lib.cvttmi_build_mips_device(self._h, pyramid.data_ptr(), layout.pyramid_bytes, image.data_ptr(), w, h,
-                                                       image.stride(0) * esz, kind, len(layout), ctypes.c_void_p(stream)), "build_mips")
+        self._check(self._lib.cvttmi_build_mips_filtered_device(self._h, pyramid.data_ptr(), layout.pyramid_bytes, image.data_ptr(), w, h,
+                                                                image.stride(0) * esz, kind, len(layout), mip_filter_value(filter),
+                                                                ctypes.c_void_p(stream)), "build_mips")
         return [image] + [pyramid[L.byteOffset: L.byteOffset + L.rowPitchBytes * L.height].view(image.dtype).view(L.height, L.width, 4)
                           for L in layout[1:]]
 
-    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None):
+    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box"):
         """(H,W,4) CUDA image -> the packed blocks of every mip level: a list of (ceil(w_L/4) * ceil(h_L/4), bytes per block)
         uint8 views, level 0 first, consecutive in one allocation (container order).  Level L equals
         encode_image(fmt, build_mips(image)[L]) byte for byte; the levels are tiled into one block tensor and searched by ONE
         encode call (groups of eight blocks are independent), so the small levels cost no launches of their own.  fmt as for
-        encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain."""
+        encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain.  mip_filter: build_mips's
+        `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L])."""
         import torch
         if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
         _, bpb, _, _ = TEXTURE_FORMATS[fmt]
-        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream)
+        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream, filter=mip_filter)
         image = images[0]
         esz = image.element_size()
         layout = mip_layout(int(image.shape[1]), int(image.shape[0]), 4 * esz, bpb, len(images))

@@ -28,6 +28,17 @@ FORMATS = {
     "bc6hs": (16, 0x8E8E, _GL_RGB, 96),
     "bc7": (16, 0x8E8C, _GL_RGBA, 98),              # GL_COMPRESSED_RGBA_BPTC_UNORM
 }
+# name -> (GL internal format, DXGI format or None) of the format's sRGB form: what `srgb=True` writes.  The readers take both
+# codes and return the same name; colour_space tells them apart.  Formats not listed here have no sRGB code.
+SRGB_FORMATS = {
+    "etc2": (0x9275, None),              # GL_COMPRESSED_SRGB8_ETC2
+    "etc2punchthrough": (0x9277, None),  # GL_COMPRESSED_SRGB8_PUNCHTHROUGH_ALPHA1_ETC2
+    "etc2rgba": (0x9279, None),          # GL_COMPRESSED_SRGB8_ALPHA8_ETC2_EAC
+    "bc1": (0x8C4D, 72),                 # GL_COMPRESSED_SRGB_ALPHA_S3TC_DXT1_EXT / DXGI_FORMAT_BC1_UNORM_SRGB
+    "bc2": (0x8C4E, 75),
+    "bc3": (0x8C4F, 78),
+    "bc7": (0x8E8D, 99),                 # GL_COMPRESSED_SRGB_ALPHA_BPTC_UNORM
+}
 # the names the reference's packer uses on its command line (etc2packer.cpp:34-42)
 ALIASES = {"etc2rgb": "etc2"}
 
@@ -42,6 +53,39 @@ def canonical(fmt):
     return fmt
 
 
+def _codes(fmt, srgb):
+    """(GL internal format, DXGI format or None) to write for a canonical format name"""
+    if not srgb:
+        return FORMATS[fmt][1], FORMATS[fmt][3]
+    if fmt not in SRGB_FORMATS:
+        raise ValueError("%s has no sRGB format code" % fmt)
+    return SRGB_FORMATS[fmt]
+
+
+def _gl_names(internal):
+    return [n for n, v in FORMATS.items() if v[1] == internal] or [n for n, v in SRGB_FORMATS.items() if v[0] == internal]
+
+
+def _dxgi_names(dxgi):
+    return [n for n, v in FORMATS.items() if v[3] == dxgi] or [n for n, v in SRGB_FORMATS.items() if v[1] == dxgi]
+
+
+def colour_space(path_or_bytes):
+    """"srgb" if a KTX or DDS file carries the sRGB code of its format (written with srgb=True), "linear" otherwise"""
+    raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+    if raw[:12] == _KTX_ID:
+        internal = struct.unpack_from("<13I", raw, 12)[4]
+        if not _gl_names(internal):
+            raise ValueError("unsupported glInternalFormat 0x%x" % internal)
+        return "srgb" if any(v[0] == internal for v in SRGB_FORMATS.values()) else "linear"
+    if raw[:4] == _DDS_MAGIC and raw[84:88] == b"DX10":
+        dxgi, = struct.unpack_from("<I", raw, 128)
+        if not _dxgi_names(dxgi):
+            raise ValueError("unsupported DXGI format %d" % dxgi)
+        return "srgb" if any(v[1] == dxgi for v in SRGB_FORMATS.values()) else "linear"
+    raise ValueError("neither a KTX 1.1 nor a DX10 DDS file")
+
+
 def _payload(fmt, width, height, packed):
     per = FORMATS[fmt][0]
     bw, bh = (width + 3) // 4, (height + 3) // 4
@@ -53,18 +97,19 @@ def _payload(fmt, width, height, packed):
     return data
 
 
-def ktx_bytes(fmt, width, height, packed):
-    """KTX 1.1 file image: the 64-byte header of etc2packer.cpp:123-147, imageSize, blocks."""
+def ktx_bytes(fmt, width, height, packed, srgb=False):
+    """KTX 1.1 file image: the 64-byte header of etc2packer.cpp:123-147, imageSize, blocks.  srgb: write the format's sRGB
+    code (SRGB_FORMATS; ValueError for a format without one) -- a mark for the sampler, the blocks are the same."""
     fmt = canonical(fmt)
+    internal, base = _codes(fmt, srgb)[0], FORMATS[fmt][2]
     data = _payload(fmt, width, height, packed)
-    _, internal, base, _ = FORMATS[fmt]
     header = _KTX_ID + struct.pack("<13I", 0x04030201, 0, 1, 0, internal, base, width, height, 0, 0, 1, 1, 0)
     return header + struct.pack("<I", data.size) + data.tobytes()
 
 
-def write_ktx(path, fmt, width, height, packed):
+def write_ktx(path, fmt, width, height, packed, srgb=False):
     with open(path, "wb") as f:
-        f.write(ktx_bytes(fmt, width, height, packed))
+        f.write(ktx_bytes(fmt, width, height, packed, srgb))
 
 
 def read_ktx(path_or_bytes):
@@ -76,7 +121,7 @@ def read_ktx(path_or_bytes):
     if f[0] != 0x04030201:
         raise ValueError("big-endian KTX is not supported")
     internal, width, height, kv = f[4], f[6], f[7], f[12]
-    names = [n for n, v in FORMATS.items() if v[1] == internal]
+    names = _gl_names(internal)
     if not names:
         raise ValueError("unsupported glInternalFormat 0x%x" % internal)
     off = 64 + kv
@@ -86,12 +131,12 @@ def read_ktx(path_or_bytes):
     return names[0], width, height, blocks
 
 
-def dds_bytes(fmt, width, height, packed):
-    """DDS with the DX10 extension header (BC formats only): one 2-D surface, one mip level."""
+def dds_bytes(fmt, width, height, packed, srgb=False):
+    """DDS with the DX10 extension header (BC formats only): one 2-D surface, one mip level.  srgb: as for ktx_bytes."""
     fmt = canonical(fmt)
-    per, _, _, dxgi = FORMATS[fmt]
-    if dxgi is None:
+    if FORMATS[fmt][3] is None:
         raise ValueError("%s has no DXGI format; use KTX" % fmt)
+    dxgi = _codes(fmt, srgb)[1]
     data = _payload(fmt, width, height, packed)
     DDSD_CAPS, DDSD_HEIGHT, DDSD_WIDTH, DDSD_PIXELFORMAT, DDSD_LINEARSIZE = 0x1, 0x2, 0x4, 0x1000, 0x80000
     flags = DDSD_CAPS | DDSD_HEIGHT | DDSD_WIDTH | DDSD_PIXELFORMAT | DDSD_LINEARSIZE
@@ -103,9 +148,9 @@ def dds_bytes(fmt, width, height, packed):
     return _DDS_MAGIC + header + dx10 + data.tobytes()
 
 
-def write_dds(path, fmt, width, height, packed):
+def write_dds(path, fmt, width, height, packed, srgb=False):
     with open(path, "wb") as f:
-        f.write(dds_bytes(fmt, width, height, packed))
+        f.write(dds_bytes(fmt, width, height, packed, srgb))
 
 
 def read_dds(path_or_bytes):
@@ -114,7 +159,7 @@ def read_dds(path_or_bytes):
         raise ValueError("not a DX10 DDS file")
     height, width = struct.unpack_from("<2I", raw, 12)
     dxgi, = struct.unpack_from("<I", raw, 128)
-    names = [n for n, v in FORMATS.items() if v[3] == dxgi]
+    names = _dxgi_names(dxgi)
     if not names:
         raise ValueError("unsupported DXGI format %d" % dxgi)
     per = FORMATS[names[0]][0]
@@ -138,19 +183,20 @@ def _mip_payloads(fmt, width, height, levels):
     return [_payload(fmt, w, h, packed) for (w, h), packed in zip(mip_sizes(width, height, len(levels)), levels)]
 
 
-def ktx_mips_bytes(fmt, width, height, levels):
+def ktx_mips_bytes(fmt, width, height, levels, srgb=False):
     """KTX 1.1 with numberOfMipmapLevels = len(levels): per level a uint32 imageSize and its blocks (what
-    Context.encode_mips returns, level 0 first).  Blocks are 8 or 16 bytes, so the mip padding to 4 bytes is always empty."""
+    Context.encode_mips returns, level 0 first).  Blocks are 8 or 16 bytes, so the mip padding to 4 bytes is always empty.
+    srgb: as for ktx_bytes."""
     fmt = canonical(fmt)
+    internal, base = _codes(fmt, srgb)[0], FORMATS[fmt][2]
     data = _mip_payloads(fmt, width, height, levels)
-    _, internal, base, _ = FORMATS[fmt]
     header = _KTX_ID + struct.pack("<13I", 0x04030201, 0, 1, 0, internal, base, width, height, 0, 0, 1, len(data), 0)
     return header + b"".join(struct.pack("<I", d.size) + d.tobytes() for d in data)
 
 
-def write_ktx_mips(path, fmt, width, height, levels):
+def write_ktx_mips(path, fmt, width, height, levels, srgb=False):
     with open(path, "wb") as f:
-        f.write(ktx_mips_bytes(fmt, width, height, levels))
+        f.write(ktx_mips_bytes(fmt, width, height, levels, srgb))
 
 
 def read_ktx_mips(path_or_bytes):
@@ -169,13 +215,14 @@ def read_ktx_mips(path_or_bytes):
     return name, width, height, levels
 
 
-def dds_mips_bytes(fmt, width, height, levels):
+def dds_mips_bytes(fmt, width, height, levels, srgb=False):
     """DDS (DX10 header) with dwMipMapCount = len(levels): the levels' blocks one after the other behind the headers.  More
-    than one level sets DDSD_MIPMAPCOUNT and DDSCAPS_COMPLEX | DDSCAPS_MIPMAP; pitchOrLinearSize is level 0's size."""
+    than one level sets DDSD_MIPMAPCOUNT and DDSCAPS_COMPLEX | DDSCAPS_MIPMAP; pitchOrLinearSize is level 0's size.
+    srgb: as for ktx_bytes."""
     fmt = canonical(fmt)
-    dxgi = FORMATS[fmt][3]
-    if dxgi is None:
+    if FORMATS[fmt][3] is None:
         raise ValueError("%s has no DXGI format; use KTX" % fmt)
+    dxgi = _codes(fmt, srgb)[1]
     data = _mip_payloads(fmt, width, height, levels)
     flags = 0x1 | 0x2 | 0x4 | 0x1000 | 0x80000  # DDSD_CAPS | HEIGHT | WIDTH | PIXELFORMAT | LINEARSIZE
     caps = 0x1000  # DDSCAPS_TEXTURE
@@ -189,9 +236,9 @@ def dds_mips_bytes(fmt, width, height, levels):
     return _DDS_MAGIC + header + dx10 + b"".join(d.tobytes() for d in data)
 
 
-def write_dds_mips(path, fmt, width, height, levels):
+def write_dds_mips(path, fmt, width, height, levels, srgb=False):
     with open(path, "wb") as f:
-        f.write(dds_mips_bytes(fmt, width, height, levels))
+        f.write(dds_mips_bytes(fmt, width, height, levels, srgb))
 
 
 def read_dds_mips(path_or_bytes):

@@ -9,34 +9,10 @@
 // lane 16 bytes of output (four RGBA8 or two RGBA16F texels): two 16-byte loads from each of the two input rows, one 16-byte
 // store.  It runs when both row starts, both pitches and the output width allow 16-byte accesses; everything else takes the
 // narrow kernel, one output texel per lane with texel-sized accesses.  No LDS, no scratch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mip_common.h"
 
 namespace
 {
-enum
-{
-    kRGBA8 = 0,
-    kRGBA16F = 1,
-    kRGBA8Snorm = 2
-};
-
-// four bytes at once: even and odd bytes are summed in 16-bit fields (4 * 255 + 2 fits).  int8 bytes become offset binary
-// (v + 128) first: the four offsets add 512, a multiple of 4, so the unsigned rule gives floor((sum + 2) / 4) + 128.
-template <int KIND>
-__device__ __forceinline__ uint32_t box4x8(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-    const uint32_t bias = KIND == kRGBA8Snorm ? 0x80808080u : 0u;
-    a ^= bias;
-    b ^= bias;
-    c ^= bias;
-    d ^= bias;
-    const uint32_t m = 0x00ff00ffu;
-    const uint32_t even = (a & m) + (b & m) + (c & m) + (d & m) + 0x00020002u;
-    const uint32_t odd = ((a >> 8) & m) + ((b >> 8) & m) + ((c >> 8) & m) + ((d >> 8) & m) + 0x00020002u;
-    return (((even >> 2) & m) | (((odd >> 2) & m) << 8)) ^ bias;
-}
-
 __device__ __forceinline__ float halfToFloat(uint32_t bits)
 {
     return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(bits)));
@@ -137,26 +113,13 @@ template <int KIND>
 hipError_t launchDownsample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
                             hipStream_t stream)
 {
-    const uint32_t texel = KIND == kRGBA16F ? 8u : 4u;
-    const uint32_t dstW = srcW > 1u ? srcW >> 1 : 1u, dstH = srcH > 1u ? srcH >> 1 : 1u;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | srcPitch | dstPitch |
-                           ((uintptr_t)dstW * texel);
-    const bool wide = (bits & 15u) == 0 && srcW >= 2u && srcH >= 2u;
-    const uint32_t perRow = wide ? dstW / (16u / texel) : dstW; // lanes of one output row
-    // a workgroup of 256 lanes, as wide as the row needs (a power of two) and as many rows high as that leaves; at most 1024
-    // workgroups down the image (enough to fill the device at any width), the kernels' row loop takes the rows beyond
-    uint32_t bx = 1;
-    while (bx < perRow && bx < 256u)
-        bx *= 2u;
-    const uint32_t by = 256u / bx;
-    const uint32_t gy = (dstH + by - 1u) / by;
-    const dim3 block(bx, by), grid((perRow + bx - 1u) / bx, gy < 1024u ? gy : 1024u);
-    if (wide)
-        hipLaunchKernelGGL(cvttmi_downsample_wide_kernel<KIND>, grid, block, 0, stream, (const uint8_t *)d_src, srcPitch,
-                           (uint8_t *)d_dst, dstPitch, perRow, dstH);
+    const MipLaunch L = mipLaunchShape(d_src, srcPitch, d_dst, dstPitch, srcW, srcH, KIND == kRGBA16F ? 8u : 4u);
+    if (L.wide)
+        hipLaunchKernelGGL(cvttmi_downsample_wide_kernel<KIND>, L.grid, L.block, 0, stream, (const uint8_t *)d_src, srcPitch,
+                           (uint8_t *)d_dst, dstPitch, L.perRow, L.dstH);
     else
-        hipLaunchKernelGGL(cvttmi_downsample_narrow_kernel<KIND>, grid, block, 0, stream, (const uint8_t *)d_src, srcPitch,
-                           (uint8_t *)d_dst, dstPitch, srcW, srcH, dstW, dstH);
+        hipLaunchKernelGGL(cvttmi_downsample_narrow_kernel<KIND>, L.grid, L.block, 0, stream, (const uint8_t *)d_src, srcPitch,
+                           (uint8_t *)d_dst, dstPitch, srcW, srcH, L.dstW, L.dstH);
     return hipGetLastError();
 }
 } // namespace

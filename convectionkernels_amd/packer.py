@@ -1,6 +1,6 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-metrics] input output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-alphaweight] [-srgb] [-metrics] input output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
@@ -13,7 +13,10 @@ image form and is measured over the written blocks against their tiles, the clam
 -mips: the file holds the full mip chain down to 1x1 (Context.encode_mips: 2x2 box filter on the device, floor convention, every
 level from the rounded one before it, all levels searched by one encode call).  With -metrics the lines of level 0 come first,
 unchanged, then one line per further level: its PSNR over the format's channels against that level's own image.  Not for
-R11, which has no image form."""
+R11, which has no image form.
+-mipfilter box|srgb|normal, -alphaweight: the filter of the chain (Context.build_mips: "srgb" averages colour in linear light,
+"normal" renormalises a normal map, -alphaweight weights colour by alpha -- with box or srgb); either implies -mips.
+-srgb: the file carries the sRGB code of its format (container.SRGB_FORMATS).  Only a mark: level 0 and the encode are unchanged."""
 import sys
 
 import numpy as np
@@ -64,21 +67,22 @@ def encode_file(image, fmt, options=None, plan=None, ctx=None):
     return packed.cpu().numpy()
 
 
-def encode_file_mips(image, fmt, options=None, plan=None, ctx=None):
+def encode_file_mips(image, fmt, options=None, plan=None, ctx=None, mip_filter="box"):
     """(H, W, 4) uint8 numpy image -> [packed blocks of level L], the full chain, container order (not R11)"""
     import torch
     ctx = ctx or api.default_context()
-    levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan)
+    levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan, mip_filter=mip_filter)
     torch.cuda.synchronize(ctx.device)
     return [level.cpu().numpy() for level in levels]
 
 
-def measure_file_mips(image, fmt, levels, ctx=None):
+def measure_file_mips(image, fmt, levels, ctx=None, mip_filter="box"):
     """[ErrorReport of level L against its own image] for the levels encode_file_mips returned, level 0 left out"""
     import torch
     ctx = ctx or api.default_context()
     fmt = container.canonical(fmt)
-    images = ctx.build_mips(torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device), len(levels), signed=fmt in ("bc4s", "bc5s"))
+    images = ctx.build_mips(torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device), len(levels), signed=fmt in ("bc4s", "bc5s"),
+                            filter=mip_filter)
     return [ctx.measure_image(fmt, img, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
             for img, packed in zip(images[1:], levels[1:])]
 
@@ -117,6 +121,7 @@ def print_metrics(report, out=None):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     fmt, uniform, fake, quality, dds, metrics, mips, paths = "etc2rgb", False, False, None, False, False, False, []
+    mip_filter, alpha_weight, srgb = None, False, False
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -134,6 +139,13 @@ def main(argv=None):
             metrics = True
         elif a == "-mips":
             mips = True
+        elif a == "-mipfilter" and i + 1 < len(argv) and argv[i + 1] in ("box", "srgb", "normal"):
+            mip_filter = argv[i + 1]
+            i += 1
+        elif a == "-alphaweight":
+            alpha_weight = True
+        elif a == "-srgb":
+            srgb = True
         elif a == "-fakebt709":
             fake = True
         elif a.startswith("-"):
@@ -145,8 +157,16 @@ def main(argv=None):
     if len(paths) != 2:
         sys.stderr.write(USAGE + "\n")
         return 2
+    mips = mips or mip_filter is not None or alpha_weight
+    mip_filter = (mip_filter or "box") + ("+alpha" if alpha_weight else "")
     try:
         fmt = container.canonical(fmt)
+        if mip_filter not in api.MIP_FILTERS:
+            raise ValueError("-alphaweight goes with -mipfilter box or srgb")
+        if fmt in ("bc4s", "bc5s") and mip_filter not in ("box", "normal"):
+            raise ValueError("-mipfilter %s: %s averages the image as int8, which takes box or normal" % (mip_filter, fmt))
+        if srgb and fmt not in container.SRGB_FORMATS:
+            raise ValueError("-srgb: %s has no sRGB format code" % fmt)
         if mips and fmt in ("r11u", "r11s"):
             raise ValueError("-mips: %s has no image form, so no mip chain" % fmt)
         image = load_rgba8(paths[0])
@@ -164,16 +184,16 @@ def main(argv=None):
         api.ConfigureBC7EncodingPlanFromQuality(plan, quality)
     h, w = image.shape[:2]
     if mips:
-        levels = encode_file_mips(image, fmt, options, plan)
+        levels = encode_file_mips(image, fmt, options, plan, mip_filter=mip_filter)
         packed = levels[0]
-        (container.write_dds_mips if dds else container.write_ktx_mips)(paths[1], fmt, w, h, levels)
+        (container.write_dds_mips if dds else container.write_ktx_mips)(paths[1], fmt, w, h, levels, srgb)
     else:
         packed = encode_file(image, fmt, options, plan)
-        (container.write_dds if dds else container.write_ktx)(paths[1], fmt, w, h, packed)
+        (container.write_dds if dds else container.write_ktx)(paths[1], fmt, w, h, packed, srgb)
     if metrics:
         print_metrics(measure_file(image, fmt, packed, options))
         if mips:
-            for l, report in enumerate(measure_file_mips(image, fmt, levels), 1):
+            for l, report in enumerate(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), 1):
                 sys.stdout.write("mip %d %dx%d psnr %.4f dB (%s, %d texels)\n" % (l, max(1, w >> l), max(1, h >> l), report.psnr(),
                                                                                   report.channels.upper(), report.texels))
     return 0

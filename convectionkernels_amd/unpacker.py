@@ -10,6 +10,8 @@ unsigned formats any other extension is written by PIL as an RGBA image.
 -level L: decode mip level L (default 0) alone.
 -mips: decode every level of the file (Context.decode_mips: one launch for the chain) and write each with its number put before
 the extension: out.0.npy, out.1.npy, ...
+A file marked sRGB (container.colour_space, the packer's -srgb) decodes to the same texels as an unmarked one: the mark tells a
+sampler how to read the decoded bytes, the decoder does not convert them.
 R11 (r11u / r11s) has no image form and is refused."""
 import os
 import struct

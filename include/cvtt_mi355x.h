@@ -331,7 +331,26 @@ int cvttmi_compact_rows_device(cvttmi_context *ctx, void *d_out, const void *d_p
  *                              images BC4S / BC5S are encoded from.  Only the two mip calls take this constant.
  *   CVTTMI_PIXELS_RGBA16F      half -> float, ((a + b) + (c + d)) * 0.25f in that order, -> half round-to-nearest-even.  Finite
  *                              inputs are the contract: non-finite values propagate as IEEE arithmetic does, NaN bits unspecified.
- * No sRGB-aware averaging, no other filter, no alpha-coverage preservation.
+ * That is CVTTMI_MIP_FILTER_BOX, the rule of cvttmi_build_mips_device.  cvttmi_build_mips_filtered_device takes a filter; the
+ * geometry, the clamp, the rounded levels and the layout are the same for all of them, and channel 3 always takes the box rule of
+ * its kind.  Channels 0..2, for the four texels a, b, c, d of a quad:
+ *   CVTTMI_MIP_FILTER_SRGB (RGBA8)  averages in linear light.  Two tables from the sRGB EOTF lin(e) = e / 12.92 for e <= 0.04045,
+ *       ((e + 0.055) / 1.055)^2.4 otherwise, computed in double precision (tools/gen_srgb_tables.py, cvttmi_srgb_tables):
+ *         T[v] = floor(65535 lin(v / 255) + 0.5), v = 0..255;   U[k] = ceil(4 * 65535 lin((k - 0.5) / 255)), k = 1..255
+ *       S = T[a] + T[b] + T[c] + T[d];  out = encode(S) = the number of k with S >= U[k].  Four equal texels give themselves.
+ *   CVTTMI_MIP_FILTER_BOX | CVTTMI_MIP_FILTER_ALPHA_WEIGHTED (RGBA8)  A = sum of the four alphas, N = sum of value_i * alpha_i;
+ *       A == 0: the box rule; otherwise out = (2 N + A) / (2 A), unsigned integer division (the weighted mean, rounded to nearest).
+ *   CVTTMI_MIP_FILTER_SRGB | CVTTMI_MIP_FILTER_ALPHA_WEIGHTED (RGBA8)  N = sum of T[value_i] * alpha_i;  A == 0: S as for SRGB,
+ *       otherwise S = (4 N + (A >> 1)) / A, unsigned integer division in 32 bits;  out = encode(S).
+ *   CVTTMI_MIP_FILTER_NORMAL (RGBA8, RGBA8_SNORM)  renormalises.  Per texel and channel X = 2 v - 255 (RGBA8) or max(v, -127)
+ *       (SNORM); SX, SY, SZ the integer sums over the four texels; Q = SX^2 + SY^2 + SZ^2 (below 2^24).  Q == 0: the box rule for
+ *       all three channels.  Otherwise len = sqrtf((float)Q), q = (float)SX / len (IEEE single precision, correctly rounded), and
+ *       RGBA8: out = clamp((int)floorf(q * 127.5f + 128.0f), 0, 255);  SNORM: out = clamp((int)floorf(q * 127.0f + 0.5f), -127, 127)
+ *       -- the product and the sum are two separately rounded operations.
+ * RGBA8 takes every filter above, RGBA8_SNORM takes BOX and NORMAL, RGBA16F takes BOX; NORMAL | ALPHA_WEIGHTED and every other
+ * value are rejected (CVTTMI_E_INVALID with an error text, nothing written).  Otherwise the call is cvttmi_build_mips_device:
+ * the same checks, one launch per level, exactly the levels' bytes written.
+ * cvttmi_srgb_tables: host only, no context.  Copies T and U (U[k] at thresholds[k - 1]); CVTTMI_E_INVALID for a NULL pointer.
  * cvttmi_mip_layout: host only, no context.  Fills out[0 .. levels - 1] with each level's place in three buffers, and
  * out[levels] (so `out` has levels + 1 entries) with their ends = the three total sizes:
  *   the pyramid   levels 1 .. levels-1 as images with tightly pitched rows, each level starting on a 256-byte boundary of the
@@ -366,6 +385,14 @@ uint32_t cvttmi_mip_level_count(uint32_t width, uint32_t height);
 int cvttmi_mip_layout(uint32_t width, uint32_t height, int pixelFormat, uint32_t bytesPerBlock, uint32_t levels, cvttmi_mip_level *out);
 int cvttmi_build_mips_device(cvttmi_context *ctx, void *d_pyramid, size_t pyramidBytes, const void *d_image, uint32_t width,
                              uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, void *hipStream);
+#define CVTTMI_MIP_FILTER_BOX 0
+#define CVTTMI_MIP_FILTER_SRGB 1
+#define CVTTMI_MIP_FILTER_NORMAL 2
+#define CVTTMI_MIP_FILTER_ALPHA_WEIGHTED 0x100 /* a flag, OR-ed onto BOX or SRGB */
+int cvttmi_build_mips_filtered_device(cvttmi_context *ctx, void *d_pyramid, size_t pyramidBytes, const void *d_image, uint32_t width,
+                                      uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, uint32_t filter,
+                                      void *hipStream);
+int cvttmi_srgb_tables(uint16_t toLinear[256], uint32_t thresholds[255]);
 
 /* BC2 / BC3 / BC4 / BC5: cvtt::Kernels::EncodeBC2, EncodeBC3, EncodeBC4U/S, EncodeBC5U/S (reference
  * ConvectionKernels_API.cpp:101-199 -> S3TCComputer::PackRGB without alpha test, PackExplicitAlpha,
