@@ -86,8 +86,6 @@ extern "C" int cvttmi_bc6h_trace_read(unsigned *out)
 }
 #endif
 
-namespace
-{
 // Waves per SIMD the register allocator may assume (128 registers; the LDS footprint of 10 KB per wave allows four).
 #ifndef CVTT_BC6H_WAVES
 #define CVTT_BC6H_WAVES 4
@@ -103,148 +101,14 @@ namespace
 #define CVTT_BC6H_LAZY_SWITCH 2
 #endif
 
-// ceil(n / 31) for 0 <= n < 2^23: one v_mul_hi_u32.  2216757579 = (2^36 + 8213) / 31 (NOT ceil(2^36 / 31) = 2216757315):
-// x * 2216757579 / 2^36 = x / 31 + x * 8213 / (31 * 2^36), and x / 31 lies at least 1 / 31 below the next integer, so the
-// floor is that of x / 31 while x * 8213 < 2^36, i.e. for x < 8.3 million (tools/check_bc6h_quantize.py compares every value)
-__device__ __forceinline__ int ceilDiv31(int n)
-{
-    return (int)(__umulhi((u32)(n + 30), 2216757579u) >> 4);
-}
+#include "bc6h_quant.h"
 
-// QuantizeSingleEndpointElementUnsigned, BC67.cpp:2441-2445.  The reference divides elem * 64 by 31 in binary32 rounded
-// up (RoundUpForScope, BC67.cpp:2556), subtracts 32768, takes the ceiling and re-biases.  For every elem the colour-space
-// clamp lets through (0 ... 31743) that is the integer ceil(elem * 64 / 31): the quotient rounded up never passes the next
-// integer (integers below 2^24 are representable), and its distance from the integer below is at least 1/31, far above
-// half an ulp of the difference -- checked exhaustively against the float sequence by tools/check_bc6h_quantize.py.
-__device__ __forceinline__ int quantizeUnsigned(int elem, int precision)
-{
-    return ceilDiv31(elem * 64) >> (16 - precision);
-}
-
-// QuantizeSingleEndpointElementSigned, BC67.cpp:2425-2439: ceil(|elem| * 32 / 31), by the same argument (|elem| <= 31743)
-__device__ __forceinline__ int quantizeSigned(int elem, int precision)
-{
-    const bool neg = elem < 0;
-    int a = neg ? -elem : elem;
-    int i = ceilDiv31(a * 32);
-    i = i > 32767 ? 32767 : i;
-    a = (int)(((u32)i & 0xffffu) >> (16 - precision));
-    return neg ? -a : a;
-}
-
-// Unquantize*, BC67.cpp:2447-2501: returns the interpolation endpoint, `finished` = colour-space value
-__device__ __forceinline__ int unquantizeUnsigned(int comp, int precision, int &finished)
-{
-    u32 unq = (u32)comp & 0xffffu;
-    if (precision < 15)
-    {
-        unq = (((u32)comp << (16 - precision)) + (0x8000u >> precision)) & 0xffffu;
-        if (comp == 0) unq = 0;
-        if (((1 << precision) - 2) < comp) unq = 0xffffu;
-    }
-    finished = (int)((unq * 31u) >> 6);
-    return (int)unq;
-}
-
-__device__ __forceinline__ int unquantizeSigned(int comp, int precision, int &finished)
-{
-    const bool neg = comp < 0;
-    const int absComp = neg ? -comp : comp;
-    int unq, absUnq;
-    if (precision >= 16)
-    {
-        unq = comp;
-        absUnq = absComp;
-    }
-    else
-    {
-        absUnq = (int)(short)(unsigned short)((absComp << (16 - precision)) + (0x4000 >> (precision - 1)));
-        if (comp == 0) absUnq = 0;
-        if (((1 << (precision - 1)) - 2) < comp) absUnq = 0x7fff;
-        unq = neg ? -absUnq : absUnq;
-    }
-    int funq = (int)((((u32)absUnq & 0xffffu) * 31u) >> 5);
-    funq = funq > 32767 ? 32767 : funq;
-    finished = (int)(short)(neg ? -funq : funq);
-    return (int)(short)unq;
-}
-
-// TwosCLHalfToFloat, ParallelMath.h:1012-1041 -- literal bit manipulation (needed for the
-// signed format, whose negative 2CL pixel values are not valid half patterns)
-__device__ __forceinline__ float twosCLHalfToFloatBits(int v16)
-{
-    const u32 v = (u32)v16 & 0xffffu;
-    const u32 signBits = v & 0x8000u;
-    const u32 mantissa = v & 0x03ffu;
-    u32 exponent = v & 0x7c00u;
-    const bool isDenormal = exponent == 0;
-    exponent = ((exponent >> 3) + 14336u) & 0xffffu;
-    const u32 corrHigh = isDenormal ? (signBits | 14336u) : 0u;
-    const u32 highBits = signBits | exponent | (mantissa >> 3);
-    const u32 lowBits = (mantissa << 13) & 0xffffu;
-    return __uint_as_float((highBits << 16) | lowBits) - __uint_as_float(corrHigh << 16);
-}
-
-// For every finite non-negative half pattern (all the unsigned format ever sees: inputs are
-// clamped to [0, 0x7BFF], reconstructions to <= 31743) the function above equals the hardware
-// conversion, except that it halves denormals (exponent field 0) -- checked exhaustively.
-template <bool SIGNED>
-__device__ __forceinline__ float twosCLHalfToFloat(int v16)
-{
-    if (SIGNED)
-        return twosCLHalfToFloatBits(v16);
-    const float f = __half2float(__ushort_as_half((unsigned short)v16));
-    return (v16 & 0x7c00) ? f : f * 0.5f;
-}
-
-// ReconstructHDR{Signed,Unsigned}Uninverted for one channel, IndexSelectorHDR.h:34-66
-// (64 - w) * e0 + w * e1 = 64 * e0 + w * (e1 - e0): one 24-bit multiply-add per interpolant instead of two 32-bit
-// multiplications (quarter rate on gfx950) -- |e| < 2^16, w <= 64, so every term fits 24 bits
-// reconstructBase: 64 * e0 + 32, with the difference e1 - e0 computed once per round and channel
-__device__ __forceinline__ u32 mulU24(u32 a, u32 b)
-{
-    u32 r;
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// DYN: the weight is a run-time value (forced v_mad_i32_i24); otherwise a literal the compiler may fold
-template <bool SIGNED, bool DYN = true>
-__device__ __forceinline__ int reconstructFrom(int base, int diff, int weight)
-{
-    if (SIGNED)
-    {
-        int p = (DYN ? madI24(weight, diff, base) : mad24(weight, diff, base)) >> 6;
-        p = p > 32767 ? 32767 : (p < -32768 ? -32768 : p);
-        const bool neg = p < 0;
-        const int a = neg ? -p : p;
-        int scaled = (int)(__umul24((u32)a & 0xffffu, 31u) >> 5); // UnscaleHDRValueSigned, BC67.cpp:766-782
-        scaled = scaled > 32767 ? 32767 : scaled;
-        return (int)(short)(unsigned short)((u32)scaled | (neg ? 0x8000u : 0u));
-    }
-    else
-    {
-        // e < 2^16, weight <= 64: 0 <= 64 e0 + w (e1 - e0) + 32 < 2^22 + 32, so ">> 6 & 0xffff" is one v_bfe_u32 (and the mask never bites)
-        const u32 p = __builtin_amdgcn_ubfe((u32)(DYN ? madI24(weight, diff, base) : mad24(weight, diff, base)), 6u, 16u);
-        return (int)(mulU24(p, 31u) >> 6);   // UnscaleHDRValueUnsigned
-    }
-}
-template <bool SIGNED>
-__device__ __forceinline__ int reconstructChannel(int e0, int e1, int weight)
-{
-    return reconstructFrom<SIGNED, false>(e0 * 64 + 32, e1 - e0, weight);
-}
-
-// the 32-lane slice of a wave ballot that belongs to the lane's reference group (8 blocks x 4 sub-lanes)
-__device__ __forceinline__ u32 groupBits(u64 ballot, int lane) { return (u32)(ballot >> (lane & 32)); }
-// the value sub-lane Q of the lane's quad holds: v_mov_b32 with a DPP quad_perm (no LDS traffic, no address register)
-template <int Q>
-__device__ __forceinline__ u32 quadBcast(u32 v)
-{
-    return (u32)__builtin_amdgcn_mov_dpp((int)v, Q * 0x55, 0xf, 0xf, true);
-}
-// meta round m = 3 * tweak + refine pass: its tweak (m = 0 ... 11)
-__device__ __forceinline__ int tweakOf(int m) { return (m * 11) >> 5; }
-} // namespace
+// One step of the quad's argmin that ends a commit search: the winner so far is (wb, wp, WIN), the candidate sub-lane Q's
+// (localBest, localPair, LOCAL) -- LOCAL / WIN one more value that belongs to a pair, a dummy where nothing does.  Q's wins only
+// if its error is smaller, so the lower sub-lane wins on equal errors.  (A macro: as a function taking references, every
+// instantiation of the kernel schedules two instructions the other way round.)
+#define CVTT_QUAD_STEP(Q, LOCAL, WIN) { const float ob = __uint_as_float(quadBcast<Q>(__float_as_uint(localBest))); const int op = (int)quadBcast<Q>((u32)localPair); \
+                                        const u32 ol = quadBcast<Q>(LOCAL); const bool lt = ob < wb; wb = lt ? ob : wb; wp = lt ? op : wp; WIN = lt ? ol : WIN; }
 
 template <bool SIGNED, bool FAST>
 __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const uint8_t *__restrict__ blocks, uint8_t *__restrict__ out,
@@ -406,13 +270,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
         bool ok = true;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++)
-        {
-            const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
-            const int bReduced = e[1][ch] & mask & 0xffff;
-            const int d16 = (int)(short)(unsigned short)(e[1][ch] - e[0][ch]);
-            const int delta = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
-            ok = ok & (((delta + e[0][ch]) & mask & 0xffff) == bReduced);
-        }
+            ok = ok & deltaFits(mw, e[1][ch], e[0][ch], ch, mask);
         return ok;
     };
 
@@ -666,9 +524,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                         lowest = fin[1][ch] < lowest ? fin[1][ch] : lowest;
                     }
                     S.interpFixup = __ballot(lowest < 0x400) != 0;
-#ifdef CVTT_BC6H_DBG_FIXUP
-                    S.interpFixup = true;
-#endif
                 }
                 if (S.interpFixup)
                 {
@@ -715,34 +570,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
             const float l2 = lf[2] * A.w[2];
             float be = 0.0f;
             int bi = 0;
-#ifdef CVTT_BC6H_PK_SCAN
-            // two interpolants per packed instruction: the same IEEE operations on the same values (v_pk_add_f32 / v_pk_mul_f32
-            // round each half like the scalar instruction; no contraction), so the errors are bit-identical
-            typedef float pk2 __attribute__((ext_vector_type(2)));
-            const pk2 L0 = {l0, l0}, L1 = {l1, l1}, L2 = {l2, l2};
-#pragma unroll
-            for (int i = 0; i < indexRange; i += 2)
-            {
-                const pk2 I0 = {S.iw[i][0], S.iw[i + 1][0]}, I1 = {S.iw[i][1], S.iw[i + 1][1]}, I2 = {S.iw[i][2], S.iw[i + 1][2]};
-                pk2 d = L0 - I0;
-                pk2 e = d * d;
-                d = L1 - I1;
-                e = e + d * d;
-                d = L2 - I2;
-                e = e + d * d;
-                if (i == 0)
-                    be = e.x;
-                else
-                {
-                    const bool lt = e.x < be;
-                    bi = lt ? i : bi;
-                    be = __builtin_fminf(be, e.x);
-                }
-                const bool lt2 = e.y < be;
-                bi = lt2 ? i + 1 : bi;
-                be = __builtin_fminf(be, e.y);
-            }
-#else
 #pragma unroll
             for (int i = 0; i < indexRange; i++)
             {
@@ -763,7 +590,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     be = __builtin_fminf(be, e);
                 }
             }
-#endif
             return bi;
         };
         // error of the pixel reconstructed with raw index `raw` (BCCommon.h:45-79)
@@ -1049,17 +875,12 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                             }
                             if (lazy)
                                 needError = false;
-#ifdef CVTT_BC6H_DBG_NOSKIP
-                            needError = true;
-                            usableNow = true;
-#endif
 
                             // ---- duplicate-round test against the meta rounds that are known now: the earlier tweaks' rounds up to
                             // this pass (DPP from the quad's lower sub-lanes) and this chain's earlier rounds.  Only a group whose
                             // eight blocks ALL repeat an earlier round skips the round, so a fingerprint of the three words is
                             // compared, and the words themselves only if some group matches in it everywhere.
                             bool same = false;
-#ifndef CVTT_BC6H_X_NODUP // (timing experiment: invalid output)
 #pragma unroll
                             for (int r2 = 0; r2 < 3; r2++)
                             {
@@ -1082,16 +903,12 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 if (r2 < refinePass)
                                     same = same | (myFp[r2] == fp);
                             }
-#endif
                             bool dropped = false;
                             {
                                 u64 g = __ballot(same && act);
                                 g &= g >> 4;
                                 g &= g >> 8;
                                 g &= g >> 16;
-#ifdef CVTT_BC6H_DBG_NODROP
-                                g = 0;
-#endif
                                 if ((g & 0x0000000f0000000full) != 0)
                                 {
                                     __syncthreads(); // (the other sub-lanes' words of this pass are in LDS)
@@ -1199,11 +1016,8 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 for (int r = 0; r < 2; r++)
                                     lateBits |= (myFp[r] == 0u) ? (1u << r) : 0u;
                             }
-                            bool anyLate = twActive && (lateBits & ((1u << numRefineRounds) - 1u) & 3u) != 0;
+                            const bool anyLate = twActive && (lateBits & ((1u << numRefineRounds) - 1u) & 3u) != 0;
                             u32 newDrop = 0; // per group: meta rounds that ran although all eight blocks repeat an earlier round
-#ifdef CVTT_BC6H_DBG_NOLATE
-                            anyLate = false;
-#endif
 #ifdef CVTT_BC6H_TRACE
                             if (partitioned && aPrec == 6 && p == 11 && subset == 1 && blockIdx.x == (u32)(CVTT_BC6H_TRACE) / 16u)
                             {
@@ -1301,23 +1115,17 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                             const bool in = actL && ((roundValid1 >> m1) & 1u);
                             bool ok0 = in && own0, ok1 = in && own1, ok2 = in && own2;
                             const int mask = (1 << aPrec) - 1;
-                            auto fitsOne = [&](int v, int base, u32 mw, int ch) -> bool {
-                                const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
-                                const int d16 = (int)(short)(unsigned short)(v - base);
-                                const int delta = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
-                                return ((delta + base) & mask & 0xffff) == (v & mask & 0xffff);
-                            };
                             bool alive = true;
 #pragma unroll
                             for (int epi = 0; epi < 2 && alive; epi++)
 #pragma unroll
                                 for (int ch = 0; ch < 3 && alive; ch++)
                                 {
-                                    ok0 = ok0 && fitsOne(x[epi][ch], e0[0][ch], modeW0, ch);
+                                    ok0 = ok0 && deltaFits(modeW0, x[epi][ch], e0[0][ch], ch, mask);
                                     if (numModesHere > 1)
-                                        ok1 = ok1 && fitsOne(x[epi][ch], e0[0][ch], modeW1, ch);
+                                        ok1 = ok1 && deltaFits(modeW1, x[epi][ch], e0[0][ch], ch, mask);
                                     if (numModesHere > 2)
-                                        ok2 = ok2 && fitsOne(x[epi][ch], e0[0][ch], modeW2, ch);
+                                        ok2 = ok2 && deltaFits(modeW2, x[epi][ch], e0[0][ch], ch, mask);
                                     alive = __ballot(ok0 || ok1 || ok2) != 0;
                                 }
                             if (ok0 || ok1 || ok2)
@@ -1331,10 +1139,8 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                         continue; // nobody can commit anything with this partition at this precision
                     PROF_COUNT(3, 1)
                     // the block's sets (the quad's lanes looked at different rounds of subset 0) ...
-                    need0 |= (u32)__builtin_amdgcn_mov_dpp((int)need0, 0xb1, 0xf, 0xf, true); // quad_perm [1,0,3,2]
-                    need0 |= (u32)__builtin_amdgcn_mov_dpp((int)need0, 0x4e, 0xf, 0xf, true); // quad_perm [2,3,0,1]
-                    need1 |= (u32)__builtin_amdgcn_mov_dpp((int)need1, 0xb1, 0xf, 0xf, true);
-                    need1 |= (u32)__builtin_amdgcn_mov_dpp((int)need1, 0x4e, 0xf, 0xf, true);
+                    need0 = quadOr(need0);
+                    need1 = quadOr(need1);
                     if (!perBlockReplay)
                     {
                         // ... and with three modes the group's: a block that is better but illegal keeps its group's mode loop going
@@ -1371,8 +1177,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 for (int ch = 0; ch < 3; ch++)
                                 {
                                     const int q0 = was ? rq[1][ch] : rq[0][ch], q1 = was ? rq[0][ch] : rq[1][ch];
-                                    unq[0][ch] = SIGNED ? unquantizeSigned(q0, aPrec, fin[0][ch]) : unquantizeUnsigned(q0, aPrec, fin[0][ch]);
-                                    unq[1][ch] = SIGNED ? unquantizeSigned(q1, aPrec, fin[1][ch]) : unquantizeUnsigned(q1, aPrec, fin[1][ch]);
+                                    unquantizeBoth<SIGNED>(q0, q1, aPrec, unq, fin, ch);
                                 }
                                 Selector S;
                                 setupSelector(unq, fin, S);
@@ -1399,10 +1204,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                 // ---- delta-coding legality + commit, BC67.cpp:2914-2986 (the four lanes of a quad do the same) ----
                 if (!usable0)
                     continue;
-#ifdef CVTT_BC6H_X_NOCOMMIT // (timing experiment: invalid output)
-                if (p != 31)
-                    continue;
-#endif
                 const int numMeta1 = partitioned ? 12 : 1;
                 // cheapest valid subset-1 round: no combination with meta0 can beat the best unless this one does.  Every sub-lane
                 // looks at the three rounds of its own chain, the quad takes the minimum (sseMin-free: no NaN among errors that count,
@@ -1418,10 +1219,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                         if (((roundValid1 >> (3 * tw + r)) & 1u) && e < minErr1)
                             minErr1 = e;
                     }
-                    float o = __uint_as_float((u32)__builtin_amdgcn_mov_dpp((int)__float_as_uint(minErr1), 0xb1, 0xf, 0xf, true));
-                    minErr1 = o < minErr1 ? o : minErr1;
-                    o = __uint_as_float((u32)__builtin_amdgcn_mov_dpp((int)__float_as_uint(minErr1), 0x4e, 0xf, 0xf, true));
-                    minErr1 = o < minErr1 ? o : minErr1;
+                    minErr1 = quadMin(minErr1);
                 }
                 // Can ANY round of subset 0 of any block of the wave beat its block's best with that?  Each sub-lane asks for its own
                 // three rounds; when nobody can, the loop below would pass every meta0 without touching anything (its first test).
@@ -1447,12 +1245,9 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     const u32 mw = modeW0;
                     const bool transformed = (mw & 16u) != 0;
                     const int mask = (1 << aPrec) - 1;
-                    auto fitsOne = [&](int v, int base, int ch) -> bool {
-                        const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
-                        const int d16 = (int)(short)(unsigned short)(v - base);
-                        const int delta = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
-                        return ((delta + base) & mask & 0xffff) == (v & mask & 0xffff);
-                    };
+                    // (deltaFits bound to this mode here, not at its call: as a direct call one instantiation schedules 48 multiplications of
+                    // the single-subset interpolant table in another order)
+                    auto fits = [&](int v, int base, int ch) -> bool { return deltaFits(mw, v, base, ch, mask); };
                     float localBest = bestError;
                     int localPair = -1; // meta0 * 16 + meta1
 #pragma unroll 1
@@ -1492,7 +1287,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 for (int epi = 0; epi < 2; epi++)
 #pragma unroll
                                     for (int ch = 0; ch < 3; ch++)
-                                        ok = ok & fitsOne(x[epi][ch], e0[0][ch], ch);
+                                        ok = ok & fits(x[epi][ch], e0[0][ch], ch);
                             }
                             if (ok)
                             {
@@ -1504,10 +1299,8 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     // the quad's winner (all four lanes end up with the same)
                     float wb = __uint_as_float(quadBcast<0>(__float_as_uint(localBest)));
                     int wp = (int)quadBcast<0>((u32)localPair);
-#define CVTT_QUAD_STEP(Q) { const float ob = __uint_as_float(quadBcast<Q>(__float_as_uint(localBest))); const int op = (int)quadBcast<Q>((u32)localPair); \
-                            const bool lt = ob < wb; wb = lt ? ob : wb; wp = lt ? op : wp; }
-                    CVTT_QUAD_STEP(1) CVTT_QUAD_STEP(2) CVTT_QUAD_STEP(3)
-#undef CVTT_QUAD_STEP
+                    u32 none = 0; // (nothing else belongs to a pair here)
+                    CVTT_QUAD_STEP(1, none, none) CVTT_QUAD_STEP(2, none, none) CVTT_QUAD_STEP(3, none, none)
                     const bool improved = (wp >= 0) & (wb < bestError);
                     if (__ballot(improved) != 0)
                     {
@@ -1529,7 +1322,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 if (transformed)
                                 {
                                     // the deltas the mode stores (they fit: the pair is legal)
-                                    const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
+                                    const int lost = lostBitsOf(mw, ch);
 #pragma unroll
                                     for (int sb = 0; sb < 2; sb++)
 #pragma unroll
@@ -1537,8 +1330,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                         {
                                             if ((sb == 0 && epi == 0) || (sb == 1 && !partitioned))
                                                 continue;
-                                            const int d16 = (int)(short)(unsigned short)(enc[sb][epi][ch] - enc[0][0][ch]);
-                                            enc[sb][epi][ch] = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
+                                            enc[sb][epi][ch] = deltaOf(enc[sb][epi][ch], enc[0][0][ch], lost);
                                         }
                                 }
                             }
@@ -1548,11 +1340,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     }
                     continue;
                 }
-#ifdef CVTT_BC6H_X_NOCOMMIT3 // (timing experiment: invalid output)
-                if (p != 31)
-                    continue;
-#endif
-#ifndef CVTT_BC6H_X_SEQ3
                 if (partitioned)
                 {
                     // ---- SEVERAL modes at this precision (8 and 11 bits).  What the mode loop below leaves behind, worked out
@@ -1568,12 +1355,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     // for one in between S depends on the pairs before X -- when such a mate could raise the mode, the wave takes the
                     // pair-by-pair loop below instead (nothing has been written by then). ----
                     const int mask = (1 << aPrec) - 1;
-                    auto fitsOne = [&](u32 mw, int v, int base, int ch) -> bool {
-                        const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
-                        const int d16 = (int)(short)(unsigned short)(v - base);
-                        const int delta = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
-                        return ((delta + base) & mask & 0xffff) == (v & mask & 0xffff);
-                    };
                     auto ownMask = [&](const int (&e)[2][3]) -> u32 {
                         u32 m = ownDeltaFits(e, modeW0, aPrec) ? 1u : 0u;
                         if (numModesHere > 1)
@@ -1598,7 +1379,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                             for (int epi = 0; epi < 2; epi++)
 #pragma unroll
                                 for (int ch = 0; ch < 3; ch++)
-                                    ok = ok & fitsOne(mw, x[epi][ch], e0[0][ch], ch);
+                                    ok = ok & deltaFits(mw, x[epi][ch], e0[0][ch], ch, mask);
                             m &= ok ? ~0u : ~(1u << mi);
                         }
                         return m;
@@ -1641,10 +1422,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     float wb = __uint_as_float(quadBcast<0>(__float_as_uint(localBest)));
                     int wp = (int)quadBcast<0>((u32)localPair);
                     u32 wL = quadBcast<0>(localModes);
-#define CVTT_QUAD_STEP(Q) { const float ob = __uint_as_float(quadBcast<Q>(__float_as_uint(localBest))); const int op = (int)quadBcast<Q>((u32)localPair); \
-                            const u32 ol = quadBcast<Q>(localModes); const bool lt = ob < wb; wb = lt ? ob : wb; wp = lt ? op : wp; wL = lt ? ol : wL; }
-                    CVTT_QUAD_STEP(1) CVTT_QUAD_STEP(2) CVTT_QUAD_STEP(3)
-#undef CVTT_QUAD_STEP
+                    CVTT_QUAD_STEP(1, localModes, wL) CVTT_QUAD_STEP(2, localModes, wL) CVTT_QUAD_STEP(3, localModes, wL)
                     const bool improved = (wp >= 0) & (wb < bestError);
                     if (__ballot(improved) == 0)
                         continue;
@@ -1714,7 +1492,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 enc[1][1][ch] = e1[1][ch];
                                 if (transformed)
                                 {
-                                    const int lost = (int)((mw >> (8 + 8 * ch)) & 31u);
+                                    const int lost = lostBitsOf(mw, ch);
 #pragma unroll
                                     for (int sb = 0; sb < 2; sb++)
 #pragma unroll
@@ -1722,8 +1500,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                         {
                                             if (sb == 0 && epi == 0)
                                                 continue;
-                                            const int d16 = (int)(short)(unsigned short)(enc[sb][epi][ch] - enc[0][0][ch]);
-                                            enc[sb][epi][ch] = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
+                                            enc[sb][epi][ch] = deltaOf(enc[sb][epi][ch], enc[0][0][ch], lost);
                                         }
                                 }
                             }
@@ -1735,7 +1512,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                     }
                     PROF_COUNT(7, 1)
                 }
-#endif
                 for (int meta0 = 0; meta0 < 12; meta0++)
                 {
                     const bool valid0 = ((roundValid0 >> meta0) & 1u) != 0;
@@ -1783,7 +1559,6 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                             if (__ballot(errorBetter && l0 && !groupDone) == 0)
                                 continue;
                             const bool transformed = (mw & 16u) != 0;
-                            const int lostBits[3] = {(int)((mw >> 8) & 31u), (int)((mw >> 16) & 31u), (int)((mw >> 24) & 31u)};
 
                             // Evaluate{Partitioned,Single}Legality, BC67.cpp:2597-2663
                             int enc[2][2][3];
@@ -1798,7 +1573,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                 enc[1][1][ch] = partitioned ? e1[1][ch] : 0;
                                 if (transformed)
                                 {
-                                    const int lost = lostBits[ch];
+                                    const int lost = lostBitsOf(mw, ch);
 #pragma unroll
                                     for (int s = 0; s < 2; s++)
 #pragma unroll
@@ -1807,8 +1582,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                                             if ((s == 0 && epi == 0) || (s == 1 && !partitioned))
                                                 continue;
                                             const int bReduced = enc[s][epi][ch] & mask & 0xffff;
-                                            const int d16 = (int)(short)(unsigned short)(enc[s][epi][ch] - enc[0][0][ch]);
-                                            const int delta = (int)(short)(unsigned short)((u32)d16 << lost) >> lost;
+                                            const int delta = deltaOf(enc[s][epi][ch], enc[0][0][ch], lost);
                                             enc[s][epi][ch] = delta;
                                             const int reconstructed = (delta + enc[0][0][ch]) & mask & 0xffff;
                                             legal = legal && (reconstructed == bReduced);
@@ -1840,9 +1614,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
             }
         }
     };
-#ifndef CVTT_BC6H_X_NOSINGLE // (timing experiment: invalid output)
     searchAll(std::false_type{});
-#endif
     searchAll(std::true_type{});
 
     // ---- the winner's indexes, selected again from its end points.  A round's indexes are a function of its quantised end
@@ -1894,8 +1666,7 @@ __global__ __launch_bounds__(64, CVTT_BC6H_WAVES) void cvttmi_bc6h_kernel(const 
                 }
                 const bool sw = ((bestSwap >> sb) & 1u) != 0; // back to the order the round selected its indexes in
                 const int q0 = sw ? qv[1] : qv[0], q1 = sw ? qv[0] : qv[1];
-                unqB[sb][0][ch] = SIGNED ? unquantizeSigned(q0, aPrecB, finB[sb][0][ch]) : unquantizeUnsigned(q0, aPrecB, finB[sb][0][ch]);
-                unqB[sb][1][ch] = SIGNED ? unquantizeSigned(q1, aPrecB, finB[sb][1][ch]) : unquantizeUnsigned(q1, aPrecB, finB[sb][1][ch]);
+                unquantizeBoth<SIGNED>(q0, q1, aPrecB, unqB[sb], finB[sb], ch);
             }
         float originB[2][3], axisB[2][3];
         if (FAST)
@@ -2058,3 +1829,4 @@ extern "C" hipError_t cvttmi_launch_bc6h(const void *d_blocks, void *d_out, cons
     return hipGetLastError();
 }
 #undef REFRESH_LANE
+#undef CVTT_QUAD_STEP

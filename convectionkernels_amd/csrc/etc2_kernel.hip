@@ -20,16 +20,11 @@
 // Alpha kernel: integer-only and lane independent, one lane per block.
 #include "cvtt_kernel_common.h"
 #include <type_traits>
+#include "etc2_wave.h"
+#include "etc2_metric.h"
 
 namespace
 {
-#define WAVE_SYNC()                                          \
-    do                                                       \
-    {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                     \
-    } while (0)
-
 constexpr int kMaxAttempts = 624; // 57 + 7 * 81 (reference ETC.h:38)
 
 struct EtcWaveShared
@@ -64,364 +59,7 @@ struct EtcWaveShared
     int planarRange[3][3][2];
 };
 
-// v_min_f32 of two values known not to be NaN (sums of squares read back from LDS): __builtin_fminf on loaded values makes
-// the compiler canonicalise both operands first (two v_max_f32 per minimum)
-__device__ __forceinline__ float minLoaded(float a, float b)
-{
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ int udivSmall(int n, int d)
-{
-    // exact n / d for 0 <= n < 2^16, 0 < d < 2^12 (integer divisions of ETC.cpp:446, 546, 717).  v_rcp_f32 (1 ulp) is enough:
-    // the product is within 0.02 of n / d, so the truncated value is off by at most one, which the two corrections undo
-    // (__frcp_rn is a full IEEE division sequence under -fhip-fp32-correctly-rounded-divide-sqrt: twenty instructions)
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) q--;
-    if (r >= d) q++;
-    return q;
-}
-
-// ceil(2^20 / d) for 1 <= d <= 128 (one float division with the two possible corrections, per EAC candidate)
-__device__ __forceinline__ int udivSmall20(int d)
-{
-    int q = (int)(1048576.0f * __builtin_amdgcn_rcpf((float)d));
-    int r = 1048576 - q * d;
-    if (r < 0) { q--; r += d; }
-    if (r >= d) { q++; r -= d; }
-    return r == 0 ? q : q + 1;
-}
-
 __device__ __forceinline__ u32 bswap32(u32 v) { return __builtin_bswap32(v); }
-
-// A value that is the same in every lane (a wave-wide winner, a best-so-far) moved to a scalar register: the compiler cannot
-// see the uniformity through shuffles and LDS reads and would keep one copy per lane alive across the search phases.
-__device__ __forceinline__ u32 uniU(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int uniI(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float uniF(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-// the value lane `lane` holds, `lane` the same in every lane: v_readlane_b32 (a scalar result) instead of a ds_bpermute_b32
-__device__ __forceinline__ int laneI(int v, int lane) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane)); }
-__device__ __forceinline__ float laneF(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), __builtin_amdgcn_readfirstlane(lane))); }
-// The value of lane (l ^ M), M a power of two: ds_swizzle_b32 in bit mode inside the 32-lane halves (no address register, a
-// third of the LDS-crossbar time of ds_bpermute_b32), ds_bpermute_b32 across them.  __shfl_xor computes its lane index with the
-// wave-size arithmetic of amd_warp_functions.h, whose common subexpression the compiler kept alive -- and spilled -- through the
-// whole kernel.
-template <int M>
-__device__ __forceinline__ int xorLaneI(int v)
-{
-    if (M < 32)
-        return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1f);
-    return __builtin_amdgcn_ds_bpermute((int)((threadIdx.x ^ 32u) << 2), v);
-}
-template <int M>
-__device__ __forceinline__ float xorLaneF(float v) { return __int_as_float(xorLaneI<M>(__float_as_int(v))); }
-
-// wave-wide argmin of (err, id); ties -> lowest id.  All lanes receive the winner (as scalars: what is derived from it is scalar
-// arithmetic).  The errors are sums of squares or FLT_MAX -- no NaN, no -0 -- so the lexicographic minimum of (err, id) is the
-// minimum of the errors (six ds_swizzle + v_min_f32) followed by the lowest id among the lanes that hold it: nearly always ONE
-// lane (a ballot, s_ff1, v_readlane), otherwise a second reduction over the ids.  (Round 5: the pair-at-a-time form -- two
-// swizzles, two compares, two selects per step -- was a third of the pair walk's instructions.)
-// An error that IS NaN (infinite weights: 0 * inf) would leave the lanes with different minima -- minLoaded keeps its second
-// operand on an unordered compare -- and the id without a holder: such errors count as FLT_MAX, so the id returned is always
-// one of the candidates (one v_cmp_u_f32 and a scalar branch in the common path).
-__device__ __forceinline__ void waveArgmin(float &err, int &id)
-{
-    if (__ballot(err != err) != 0)
-        err = (err == err) ? err : FLT_MAX;
-    float m = err;
-    m = minLoaded(m, xorLaneF<1>(m));
-    m = minLoaded(m, xorLaneF<2>(m));
-    m = minLoaded(m, xorLaneF<4>(m));
-    m = minLoaded(m, xorLaneF<8>(m));
-    m = minLoaded(m, xorLaneF<16>(m));
-    m = minLoaded(m, xorLaneF<32>(m));
-    const bool mine = err == m;
-    const u64 holders = __ballot(mine);
-    int best;
-    if (__popcll(holders) == 1)
-        best = __builtin_amdgcn_readlane(id, __ffsll((long long)holders) - 1);
-    else
-    {
-        int c = mine ? id : 0x7fffffff;
-#define ETC_IDMIN_STEP(M) { const int o = xorLaneI<M>(c); c = o < c ? o : c; }
-        ETC_IDMIN_STEP(1) ETC_IDMIN_STEP(2) ETC_IDMIN_STEP(4) ETC_IDMIN_STEP(8) ETC_IDMIN_STEP(16) ETC_IDMIN_STEP(32)
-#undef ETC_IDMIN_STEP
-        best = __builtin_amdgcn_readfirstlane(c);
-    }
-    err = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m)));
-    id = best;
-}
-
-// ConvertToFakeBT709, ETC.cpp:2343-2352
-__device__ __forceinline__ void toFake709(float (&yuv)[3], float r, float g, float b)
-{
-    yuv[0] = r * 0.368233989135369f + g * 1.23876274963149f + b * 0.125054068802017f;
-    yuv[1] = r * 0.5f - g * 0.4541529f - b * 0.04584709f;
-    yuv[2] = r * -0.081014709086133f - g * 0.272538676238785f + b * 0.353553390593274f;
-}
-
-// the octant search shared by ResolveTHFakeBT709Rounding and ResolveHalfBlockFakeBT709RoundingAccurate
-// (ETC.cpp:2199-2231, 2304-2326): which of the 8 cell corners is nearest to `target`; the reference's error adds the
-// chroma-U difference twice instead of squaring it
-__device__ __forceinline__ int fakeOctant(const float (&lowF)[3], const float (&highF)[3], const float (&target)[3])
-{
-    float cum[3];
-    toFake709(cum, target[0], target[1], target[2]);
-    float bestError = FLT_MAX;
-    int bestOctant = 0;
-#pragma unroll
-    for (int octant = 0; octant < 8; octant++)
-    {
-        float oy[3];
-        toFake709(oy, (octant & 1) ? highF[0] : lowF[0], (octant & 2) ? highF[1] : lowF[1], (octant & 4) ? highF[2] : lowF[2]);
-        const float d0 = oy[0] - cum[0], d1 = oy[1] - cum[1], d2 = oy[2] - cum[2];
-        const float error = d0 * d0 + d1 + d1 + d2 * d2;
-        if (error < bestError)
-            bestOctant = octant;
-        bestError = sseMin(error, bestError);
-    }
-    return bestOctant;
-}
-
-// ResolveTHFakeBT709Rounding, ETC.cpp:2286-2327
-__device__ __forceinline__ void resolveTHFake(int (&quantized)[3], const int (&targets)[3], int granularity)
-{
-    float lowF[3], highF[3], tf[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-    {
-        const int unq = (quantized[ch] << 4) | quantized[ch];
-        const int next = unq + 17 < 255 ? unq + 17 : 255;
-        lowF[ch] = (float)(int)(short)((int)(short)(unq * granularity) << 1);
-        highF[ch] = (float)(int)(short)((int)(short)(next * granularity) << 1);
-        tf[ch] = (float)targets[ch];
-    }
-    const int octant = fakeOctant(lowF, highF, tf);
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-        quantized[ch] += (octant >> ch) & 1;
-}
-
-// ResolveHalfBlockFakeBT709RoundingAccurate / Fast, ETC.cpp:2157-2284
-__device__ __forceinline__ void resolveHalfFake(int (&quantized)[3], const int (&cumulative)[3], bool isDifferential, bool accurate,
-                                                const CvttDeviceTables *__restrict__ T)
-{
-    if (accurate)
-    {
-        float lowF[3], highF[3], tf[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++)
-        {
-            const u32 cu = (u32)cumulative[ch];
-            int unq, next;
-            if (isDifferential)
-            {
-                quantized[ch] = (int)(((((cu << 5) - cu) + (cu >> 3)) & 0xffffu) >> 11);
-                unq = (quantized[ch] << 3) | (quantized[ch] >> 2);
-                const int qn = quantized[ch] + 1 < 31 ? quantized[ch] + 1 : 31;
-                next = (qn << 3) | (qn >> 2);
-            }
-            else
-            {
-                quantized[ch] = (int)(((((cu << 5) - ((cu << 1) & 0xffffu)) + (cu >> 3)) & 0xffffu) >> 12);
-                unq = (quantized[ch] << 4) | quantized[ch];
-                next = unq + 17 < 255 ? unq + 17 : 255;
-            }
-            lowF[ch] = (float)(unq << 3);
-            highF[ch] = (float)(next << 3);
-            tf[ch] = (float)cumulative[ch];
-        }
-        const int octant = fakeOctant(lowF, highF, tf);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++)
-            quantized[ch] += (octant >> ch) & 1;
-        return;
-    }
-    int fill[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-        fill[ch] = cumulative[ch] + (cumulative[ch] >> 8);
-    const int index = isDifferential ? (((fill[0] << 6) & 0xf00) | ((fill[1] << 4) & 0x0f0) | ((fill[2] >> 2) & 0x00f))
-                                     : (((fill[0] << 5) & 0xf00) | ((fill[1] << 1) & 0x0f0) | ((fill[2] >> 3) & 0x00f));
-    const int octant = T->fake709Rounding[index];
-    const int upper = isDifferential ? 31 : 15, shift = isDifferential ? 6 : 7;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-    {
-        const int q = (fill[ch] >> shift) + ((octant >> ch) & 1);
-        quantized[ch] = q < upper ? q : upper;
-    }
-}
-
-// Two f32 values that go through the same operations: two plain instructions each (default), or, with CVTT_ETC_PACKED_F32, one
-// v_pk_mul_f32 / v_pk_add_f32.  Same operations on the same values in the same order either way.  A packed instruction does two
-// values in one 4.3-cycle issue slot but never shares the slot with another wave's instruction; a plain f32 instruction shares it
-// with nearly anything (tools/valu_mix.py), and this kernel has more compares, minima and selects looking for such a partner than
-// plain f32 work.  Round 2 measured packed ahead (3.7 waves per SIMD, 24 spilled registers); round 5, with 4.2 waves and no
-// scratch: plain EncodeETC2RGBA 41.1 -> 42.6, EncodeETC2 44.1 -> 46.2, EncodeETC1 42.2 -> 44.0 Mblocks/s (profiles/r05/ab_etc2.txt).
-#ifndef CVTT_ETC_PACKED_F32
-struct EtcPair
-{
-    float x, y;
-};
-__device__ __forceinline__ EtcPair operator-(const EtcPair &a, const EtcPair &b) { return EtcPair{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ EtcPair operator+(const EtcPair &a, const EtcPair &b) { return EtcPair{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ EtcPair operator*(const EtcPair &a, const EtcPair &b) { return EtcPair{a.x * b.x, a.y * b.y}; }
-#else
-typedef float EtcPair __attribute__((ext_vector_type(2)));
-#endif
-
-struct EtcErr
-{
-    bool uniform;
-    float rw, gw, bw;
-    bool fake;
-    // the metric of most call sites: ComputeErrorFakeBT709 (ETC.cpp:82-92) first, then uniform, then weighted
-    __device__ __forceinline__ float operator()(int r, int g, int b, const int *px, const float *pw) const
-    {
-        if (fake)
-        {
-            float yuv[3];
-            toFake709(yuv, (float)r, (float)g, (float)b);
-            const float dy = yuv[0] - pw[0], du = yuv[1] - pw[1], dv = yuv[2] - pw[2];
-            return dy * dy + du * du + dv * dv;
-        }
-        return wu(r, g, b, px, pw);
-    }
-    // The weighted metric for TWO colours at once (an EtcPair: plain or packed f32, see above): each of the two does
-    // ComputeErrorWeighted's operations in its order (product, difference, squares added left to right), so both results are
-    // the numbers the scalar form gives.  Only valid when !uniform (and, where the caller would use operator(), !fake).
-    typedef EtcPair f32x2;
-    __device__ __forceinline__ void weigh2(f32x2 (&mw)[3], const int (&a)[3], const int (&b)[3]) const
-    {
-        mw[0] = f32x2{(float)a[0] * rw, (float)b[0] * rw};
-        mw[1] = f32x2{(float)a[1] * gw, (float)b[1] * gw};
-        mw[2] = f32x2{(float)a[2] * bw, (float)b[2] * bw};
-    }
-    __device__ __forceinline__ f32x2 err2(const f32x2 (&mw)[3], const float *pw) const
-    {
-        f32x2 d = mw[0] - f32x2{pw[0], pw[0]};
-        f32x2 e = d * d;
-        d = mw[1] - f32x2{pw[1], pw[1]};
-        e = e + d * d;
-        d = mw[2] - f32x2{pw[2], pw[2]};
-        e = e + d * d;
-        return e;
-    }
-    // ComputeErrorUniform / ComputeErrorWeighted, ETC.cpp:59-80.  The line colours of the T modes are measured with
-    // this even under ETC_UseFakeBT709 (ETC.cpp:600, 1133, 1150), against pre-weighted pixels that then hold luma/chroma
-    __device__ __forceinline__ float wu(int r, int g, int b, const int *px, const float *pw) const
-    {
-        if (uniform)
-        {
-            const float d0 = (float)(r - px[0]), d1 = (float)(g - px[1]), d2 = (float)(b - px[2]);
-            float e = d0 * d0;
-            e = e + d1 * d1;
-            e = e + d2 * d2;
-            return e;
-        }
-        const float dr = (float)r * rw - pw[0];
-        const float dg = (float)g * gw - pw[1];
-        const float db = (float)b * bw - pw[2];
-        return dr * dr + dg * dg + db * db;
-    }
-};
-
-__device__ __forceinline__ int planarDecode(int coeff, int ch)
-{
-    return (ch == 1) ? (((coeff << 1) | (coeff >> 6)) & 0xffff) : (((coeff << 2) | (coeff >> 4)) & 0xffff);
-}
-
-// EmitTModeBlock, ETC.cpp:2414-2460
-__device__ __forceinline__ void emitT(u32 &hi, u32 &lo, const int (&lineColor)[3], const int (&iso)[3], u32 packedSelectors, int table, bool opaque = true)
-{
-    hi = 0;
-    lo = 0;
-    const int rh = (iso[0] >> 2) & 3, rl = iso[0] & 3;
-    if (rh + rl < 4) hi |= 1u << (58 - 32); else hi |= 7u << (61 - 32);
-    hi |= (u32)rh << (59 - 32);
-    hi |= (u32)rl << (56 - 32);
-    hi |= (u32)iso[1] << (52 - 32);
-    hi |= (u32)iso[2] << (48 - 32);
-    hi |= (u32)lineColor[0] << (44 - 32);
-    hi |= (u32)lineColor[1] << (40 - 32);
-    hi |= (u32)lineColor[2] << (36 - 32);
-    hi |= (u32)((table >> 1) & 3) << (34 - 32);
-    if (opaque)
-        hi |= 1u << (33 - 32);
-    hi |= (u32)(table & 1);
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-    {
-        const int src = ((px & 3) << 2) | (px >> 2); // selectorOrder
-        const u32 sel = (packedSelectors >> (2 * src)) & 3u;
-        lo |= (sel & 1u) << px;
-        lo |= ((sel >> 1) & 1u) << (16 + px);
-    }
-}
-
-// EmitHModeBlock, ETC.cpp:2462-2563.  bc0 / bc1: 4:4:4 colours packed r << 10 | g << 5 | b.
-__device__ __forceinline__ void emitH(u32 &outHi, u32 &outLo, int bc0, int bc1, u32 sectorBits, u32 signBits, int table, bool opaque)
-{
-    if (bc0 == bc1)
-    {
-        const int lineColor[3] = {(bc0 >> 10) & 0x1f, (bc0 >> 5) & 0x1f, bc0 & 0x1f};
-        u32 packedSelectors = 0x55555555u;
-#pragma unroll
-        for (int px = 0; px < 16; px++)
-            packedSelectors |= ((signBits >> px) & 1u) << ((px * 2) + 1);
-        emitT(outHi, outLo, lineColor, lineColor, packedSelectors, table, opaque);
-        return;
-    }
-    int colors[2][3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-    {
-        colors[0][ch] = (bc0 >> ((2 - ch) * 5)) & 15;
-        colors[1][ch] = (bc1 >> ((2 - ch) * 5)) & 15;
-    }
-    if (((table & 1) == 1) != (bc0 > bc1))
-    {
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++)
-        {
-            const int t = colors[0][ch];
-            colors[0][ch] = colors[1][ch];
-            colors[1][ch] = t;
-        }
-        sectorBits ^= 0xffffu;
-    }
-    const int r1 = colors[0][0], g1a = colors[0][1] >> 1, g1b = colors[0][1] & 1, b1a = colors[0][2] >> 3, b1b = colors[0][2] & 7;
-    const int r2 = colors[1][0], g2 = colors[1][1], b2 = colors[1][2];
-    u32 hi = 0, lo = 0;
-    if ((g1a & 4) != 0 && r1 + g1a < 8) hi |= 1u << (63 - 32);
-    const int fakeDG = b1b >> 1, fakeG = b1a | (g1b << 1);
-    if (fakeG + fakeDG < 4) hi |= 1u << (50 - 32); else hi |= 7u << (53 - 32);
-    hi |= (u32)r1 << (59 - 32);
-    hi |= (u32)g1a << (56 - 32);
-    hi |= (u32)g1b << (52 - 32);
-    hi |= (u32)b1a << (51 - 32);
-    hi |= (u32)b1b << (47 - 32);
-    hi |= (u32)r2 << (43 - 32);
-    hi |= (u32)g2 << (39 - 32);
-    hi |= (u32)b2 << (35 - 32);
-    hi |= (u32)((table >> 2) & 1) << (34 - 32);
-    if (opaque)
-        hi |= 1u << (33 - 32);
-    hi |= (u32)((table >> 1) & 1);
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-    {
-        const int src2 = ((px & 3) << 2) | (px >> 2);
-        lo |= ((signBits >> src2) & 1u) << px;
-        lo |= ((sectorBits >> src2) & 1u) << (16 + px);
-    }
-    outHi = hi;
-    outLo = lo;
-}
 } // namespace
 
 #ifdef CVTT_ETC_PROFILE
@@ -593,9 +231,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
             }
         }
         u32 key = bestKey;
-#define ETC_KEYMIN_STEP(M) { const u32 o = (u32)xorLaneI<M>((int)key); key = o < key ? o : key; }
-        ETC_KEYMIN_STEP(1) ETC_KEYMIN_STEP(2) ETC_KEYMIN_STEP(4) ETC_KEYMIN_STEP(8) ETC_KEYMIN_STEP(16) ETC_KEYMIN_STEP(32)
-#undef ETC_KEYMIN_STEP
+        butterfly<1, 2, 4, 8, 16, 32>([&](auto m) { const u32 o = (u32)xorLaneI<m.value>((int)key); key = o < key ? o : key; });
         const int bestC = (int)(key & 511u);
         const int bestTable = (int)(((u32)bestC * 3277u) >> 16);
         bestBase = laneI(bestBase, bestC & 63);
@@ -664,12 +300,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
     const bool groupAll = PUNCH && (__ballot(transJ == 0xffffu) & 0xffull) == 0xffull;
     // maximum over the eight members (lanes that differ in their low three bits)
     auto groupMax = [](int v) {
-        int o = xorLaneI<1>(v);
-        v = o > v ? o : v;
-        o = xorLaneI<2>(v);
-        v = o > v ? o : v;
-        o = xorLaneI<4>(v);
-        v = o > v ? o : v;
+        butterfly<1, 2, 4>([&](auto m) { const int o = xorLaneI<m.value>(v); v = o > v ? o : v; });
         return v;
     };
 
@@ -679,10 +310,6 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
     unsigned long long profT = __builtin_readcyclecounter();
 #define DBG_TAP(i) do { const unsigned long long now = __builtin_readcyclecounter(); if (lane == 0) atomicAdd(&g_etcProf[i], now - profT); profT = now; } while (0)
 #define DBG_COUNT(i, n) do { if (lane == 0) atomicAdd(&g_etcProf[i], (unsigned long long)(n)); } while (0)
-#elif defined(CVTT_ETC_DEBUG)
-    float *dbg = reinterpret_cast<float *>(A.debug) + (size_t)blockIndex * 8;
-#define DBG_TAP(i) do { if (lane == 0 && A.debug) dbg[i] = bestError; } while (0)
-#define DBG_COUNT(i, n) do {} while (0)
 #else
 #define DBG_TAP(i) do {} while (0)
 #define DBG_COUNT(i, n) do {} while (0)
@@ -1096,7 +723,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                         lc[2][ch] = u - modifier > 0 ? u - modifier : 0;
                     }
                     float error = 0.0f;
-                    EtcErr::f32x2 lw01[3];
+                    v2f lw01[3];
                     E.weigh2(lw01, lc[0], lc[1]);
                     // the metric is a run-time flag: decided once per pass, not per pixel (as a test inside the loop it was four
                     // branches per pixel and kept the sixteen trips from being unrolled)
@@ -1111,7 +738,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                             float e3[3];
                             if (!UNI)
                             {
-                                const EtcErr::f32x2 e01 = EE.err2(lw01, S.pw[px]);
+                                const v2f e01 = EE.err2(lw01, S.pw[px]);
                                 e3[0] = e01.x;
                                 e3[1] = e01.y;
                             }
@@ -1231,9 +858,9 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                 float e3[3];
                 if (!E.uniform)
                 {
-                    EtcErr::f32x2 lw01[3];
+                    v2f lw01[3];
                     E.weigh2(lw01, lc[0], lc[1]);
-                    const EtcErr::f32x2 e01 = E.err2(lw01, S.pw[px]);
+                    const v2f e01 = E.err2(lw01, S.pw[px]);
                     e3[0] = e01.x;
                     e3[1] = e01.y;
                 }
@@ -1373,7 +1000,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                         c0[ch] = u + modifier < 255 ? u + modifier : 255;
                         c1[ch] = u - modifier > 0 ? u - modifier : 0;
                     }
-                    EtcErr::f32x2 cw[3];
+                    v2f cw[3];
                     E.weigh2(cw, c0, c1);
                     // (the metric flag is decided once per pass, as in the T modes)
                     auto hPixels = [&](auto uniTag) {
@@ -1386,7 +1013,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                             float e0, e1;
                             if (!FAKE && !UNI)
                             {
-                                const EtcErr::f32x2 e01 = EE.err2(cw, S.pw[px]);
+                                const v2f e01 = EE.err2(cw, S.pw[px]);
                                 e0 = e01.x;
                                 e1 = e01.y;
                             }
@@ -1476,9 +1103,9 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                     float e0, e1;
                     if (!FAKE && !E.uniform)
                     {
-                        EtcErr::f32x2 cw[3];
+                        v2f cw[3];
                         E.weigh2(cw, c0, c1);
-                        const EtcErr::f32x2 e01 = E.err2(cw, S.pw[px]);
+                        const v2f e01 = E.err2(cw, S.pw[px]);
                         e0 = e01.x;
                         e1 = e01.y;
                     }
@@ -1756,17 +1383,16 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                     if (!punch && !FAKE && !E.uniform)
                     {
                         // the weighted metric (ComputeErrorWeighted, ETC.cpp:70-80), the four paint colours of a candidate two
-                        // at a time (EtcPair): each value goes through the reference's operations in the reference's order
+                        // at a time (v2f): each value goes through the reference's operations in the reference's order
                         // (product, difference, squares added left to right), so the sums are the same numbers; 16 packed
                         // instructions per pixel instead of 32 plain ones
-                        typedef EtcPair pk2;
-                        pk2 mw01[3], mw23[3];
+                        v2f mw01[3], mw23[3];
 #pragma unroll
                         for (int ch = 0; ch < 3; ch++)
                         {
                             const float w = ch == 0 ? E.rw : (ch == 1 ? E.gw : E.bw);
-                            mw01[ch] = pk2{(float)modified[0][ch] * w, (float)modified[1][ch] * w};
-                            mw23[ch] = pk2{(float)modified[2][ch] * w, (float)modified[3][ch] * w};
+                            mw01[ch] = v2f{(float)modified[0][ch] * w, (float)modified[1][ch] * w};
+                            mw23[ch] = v2f{(float)modified[2][ch] * w, (float)modified[3][ch] * w};
                         }
                         // two pixels per trip (the pair of a half-block row for flip 0, neighbours for flip 1): the loop is not
                         // unrolled because of its exit, and per pixel its bookkeeping was a fifth of the body
@@ -1778,15 +1404,15 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
                             const int spx = sp2 * 2 + h;
                             const int px = flip == 0 ? ((spx >> 1) * 4 + (spx & 1) + sector * 2) : (spx + sector * 8);
                             const float *pw = S.pw[px];
-                            const pk2 p0 = pk2{pw[0], pw[0]}, p1 = pk2{pw[1], pw[1]}, p2 = pk2{pw[2], pw[2]};
-                            pk2 dd = mw01[0] - p0;
-                            pk2 e01 = dd * dd;
+                            const v2f p0 = v2f{pw[0], pw[0]}, p1 = v2f{pw[1], pw[1]}, p2 = v2f{pw[2], pw[2]};
+                            v2f dd = mw01[0] - p0;
+                            v2f e01 = dd * dd;
                             dd = mw01[1] - p1;
                             e01 = e01 + dd * dd;
                             dd = mw01[2] - p2;
                             e01 = e01 + dd * dd;
                             dd = mw23[0] - p0;
-                            pk2 e23 = dd * dd;
+                            v2f e23 = dd * dd;
                             dd = mw23[1] - p1;
                             e23 = e23 + dd * dd;
                             dd = mw23[2] - p2;
@@ -2469,232 +2095,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// EAC 8-bit alpha: CompressETC2AlphaBlockInternal (ETC.cpp:1902-2085), QuantizeETC2Alpha 2366-2411.
-// KIND 0: 8-bit alpha of PixelBlockU8 (EncodeETC2Alpha / the alpha half of EncodeETC2RGBA);
-// KIND 1 / 2: unsigned / signed 11-bit EAC of PixelBlockScalarS16 (EncodeETC2Alpha11, CompressEACBlock ETC.cpp:2087-2114)
-// SPREAD = false: one lane per block (the throughput form: a wave's 64 blocks share every table word).
-// SPREAD = true: sixteen lanes per block, lane t searches modifier table t, and a 16-lane minimum of (error, table) picks the
-// winner -- the reference walks the tables in ascending order and keeps the first minimum, i.e. the lowest table among equal
-// errors.  The same instructions per block, but a sixteenth of the latency: what a call with a handful of blocks (the
-// reference's 8-block convention, ConvectionKernels_API.cpp:246-256, 270-286) waits for (213 -> 25 us at 16 blocks).
-template <int KIND, bool SPREAD>
-__global__ __launch_bounds__(64) void cvttmi_eac_alpha_kernel(const uint8_t *__restrict__ blocks, uint8_t *__restrict__ out,
-                                                             const CvttEtcArgs A, const CvttDeviceTables *__restrict__ T)
-{
-    constexpr bool is11 = KIND != 0, isSigned = KIND == 2;
-    const u32 blockIndex = SPREAD ? blockIdx.x * 4u + (threadIdx.x >> 4) : blockIdx.x * 64u + threadIdx.x;
-    const bool valid = blockIndex < A.numBlocks;
-    int pixel[16];
-    if (!is11)
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(blocks + (size_t)(valid ? blockIndex : 0u) * 64u);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-        {
-            const uint4 v = src[i];
-            pixel[4 * i + 0] = (int)(v.x >> 24);
-            pixel[4 * i + 1] = (int)(v.y >> 24);
-            pixel[4 * i + 2] = (int)(v.z >> 24);
-            pixel[4 * i + 3] = (int)(v.w >> 24);
-        }
-    }
-    else
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(blocks + (size_t)(valid ? blockIndex : 0u) * 32u);
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-        {
-            const uint4 v = src[i];
-            const u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-            {
-                int x = (int)(short)((w[j >> 1] >> (16 * (j & 1))) & 0xffffu);
-                // shifted ranges: signed 1..2047, unsigned 0..2047
-                if (isSigned)
-                {
-                    x = (x > 1023 ? 1023 : x) + 1024;
-                    x = x < 1 ? 1 : x;
-                }
-                else
-                    x = x > 2047 ? 2047 : (x < 0 ? 0 : x);
-                pixel[8 * i + j] = x;
-            }
-        }
-    }
-    int minAlpha = is11 ? 2047 : 255, maxAlpha = 0;
-#pragma unroll
-    for (int px = 0; px < 16; px++)
-    {
-        minAlpha = pixel[px] < minAlpha ? pixel[px] : minAlpha;
-        maxAlpha = pixel[px] > maxAlpha ? pixel[px] : maxAlpha;
-    }
-    const int alphaSpan = maxAlpha - minAlpha;
-    const int midTimes2 = maxAlpha + minAlpha;
-
-    u32 bestTotalError = 0x7fffffffu;
-    int bestTable = 0, bestBase = 0, bestMultiplier = 0;
-    u32 bestIdxLo = 0, bestIdxHi = 0; // 3 bits per pixel
-
-    for (int tableIter = 0; tableIter < (SPREAD ? 1 : 16); tableIter++)
-    {
-        const int tableIndex = SPREAD ? (int)(threadIdx.x & 15u) : tableIter;
-        const int pos[4] = {T->eacPositive[tableIndex][0], T->eacPositive[tableIndex][1], T->eacPositive[tableIndex][2], T->eacPositive[tableIndex][3]};
-        // the table's row of the rounding table (13 entries of 2 bits) and its four positive modifiers as two wave-uniform
-        // words: a pixel's lookups are bit-field extracts instead of a per-lane byte load and a select chain
-        u32 roundBits = 0;
-        for (int i = 0; i < 13; i++)
-            roundBits |= (u32)T->eacRounding[tableIndex][i] << (2 * i);
-        u32 posWord = (u32)(pos[0] | (pos[1] << 8) | (pos[2] << 16) | (pos[3] << 24));
-        if (!SPREAD)
-        {
-            roundBits = (u32)__builtin_amdgcn_readfirstlane((int)roundBits);
-            posWord = (u32)__builtin_amdgcn_readfirstlane((int)posWord);
-        }
-        for (int r = 0; r < 10; r++)
-        {
-            const int subrange = r % 3, mainRange = r / 3;
-            const int maxOffset = T->eacPositive[tableIndex][3 - mainRange - (subrange & 1)];
-            const int minOffset = -(int)T->eacPositive[tableIndex][3 - mainRange - ((subrange >> 1) & 1)] - 1;
-            const int offsetSpan = maxOffset - minOffset;
-            int minMultiplier = udivSmall(alphaSpan, offsetSpan);
-            if (is11)
-            {
-                minMultiplier = minMultiplier > 112 ? 112 : minMultiplier;
-                minMultiplier &= 120;
-            }
-            else
-            {
-                minMultiplier = minMultiplier > 14 ? 14 : minMultiplier;
-                minMultiplier = minMultiplier < 1 ? 1 : minMultiplier;
-            }
-            for (int mo = 0; mo < 2; mo++)
-            {
-                int multiplier = minMultiplier;
-                if (is11)
-                {
-                    if (mo == 1)
-                        multiplier += 8;
-                    else
-                        multiplier = multiplier < 1 ? 1 : multiplier;
-                }
-                else
-                    multiplier += mo;
-                int base2 = midTimes2 - multiplier * maxOffset - multiplier * minOffset; // all lanes stay inside 16 bits
-                int baseAlpha;
-                if (is11)
-                {
-                    if (isSigned)
-                        base2 += 8;
-                    const int lo2 = isSigned ? 16 : 0;
-                    base2 = base2 < lo2 ? lo2 : (base2 > 4095 ? 4095 : base2);
-                    baseAlpha = (base2 >> 1) & 2040;
-                    if (!isSigned)
-                        baseAlpha += 4;
-                }
-                else
-                {
-                    base2 = base2 < 0 ? 0 : (base2 > 510 ? 510 : base2);
-                    baseAlpha = (base2 + 1) >> 1;
-                }
-                // lookup / multiplier for lookup < 2^12, multiplier <= 128: (lookup * ceil(2^20 / multiplier)) >> 20 is exact
-                // (the excess of the magic number adds less than lookup / 2^20 < 1/256 to a quotient whose fraction is at most
-                // 127/128), one 24-bit multiply and a shift per pixel; the magic number is per candidate
-                const u32 magic = (u32)udivSmall20(multiplier);
-                u32 totalError = 0; // (only the error: the winner's indexes are worked out again after the search)
-#pragma unroll
-                for (int px = 0; px < 16; px++)
-                {
-                    const int a = pixel[px];
-                    const int refl2 = (a - baseAlpha) * 2 + multiplier;
-                    const int absv = refl2 < 0 ? -refl2 : refl2;
-                    const int lookup = absv >> 1;
-                    int li = (int)(__umul24((u32)lookup, magic) >> 20);
-                    li = li >= 13 ? 12 : li;
-                    const int index = (int)((roundBits >> (2 * li)) & 3u);
-                    const int pOff = (int)((posWord >> (8 * index)) & 0xffu);
-                    const int sign = refl2 < 0 ? -1 : 0;
-                    const int quantizedOffset = (pOff ^ sign) * multiplier;
-                    int q = baseAlpha + quantizedOffset;
-                    const int qLo = (is11 && isSigned) ? 1 : 0, qHi = is11 ? 2047 : 255;
-                    q = q < qLo ? qLo : (q > qHi ? qHi : q);
-                    const int d = q - a;
-                    totalError += (u32)(d * d);
-                }
-                if (totalError < bestTotalError)
-                {
-                    bestTotalError = totalError;
-                    bestTable = tableIndex;
-                    bestBase = baseAlpha;
-                    bestMultiplier = multiplier;
-                }
-            }
-        }
-    }
-    if (SPREAD)
-    {
-        // (error, table) as one word: the error of 16 pixels stays below 2^27 (16 x 2047^2)
-        u32 key = (bestTotalError << 4) | (u32)bestTable;
-#pragma unroll
-        for (int step = 1; step < 16; step <<= 1)
-        {
-            const u32 o = (u32)__shfl_xor((int)key, step);
-            key = o < key ? o : key;
-        }
-        const int src = (int)((threadIdx.x & ~15u) | (key & 15u));
-        bestTable = (int)(key & 15u);
-        bestBase = __shfl(bestBase, src);
-        bestMultiplier = __shfl(bestMultiplier, src);
-    }
-    // the winner's indexes (the operations of the candidate loop, once)
-    {
-        const u32 magic = (u32)udivSmall20(bestMultiplier);
-#pragma unroll
-        for (int px = 0; px < 16; px++)
-        {
-            const int refl2 = (pixel[px] - bestBase) * 2 + bestMultiplier;
-            const int absv = refl2 < 0 ? -refl2 : refl2;
-            int li = (int)(__umul24((u32)(absv >> 1), magic) >> 20);
-            li = li >= 13 ? 12 : li;
-            const int index = T->eacRounding[bestTable][li];
-            const u32 code = (u32)(index + 4 - ((refl2 < 0 ? -1 : 0) & 4));
-            if (px < 8)
-                bestIdxLo |= code << (3 * px);
-            else
-                bestIdxHi |= code << (3 * (px - 8));
-        }
-    }
-    if (is11)
-    {
-        bestMultiplier >>= 3;
-        if (isSigned)
-            bestBase ^= 0x80;
-    }
-    if (valid && (!SPREAD || (threadIdx.x & 15u) == 0))
-    {
-        // 16 x 3-bit indexes, column-major pixel order, MSB first (ETC.cpp:2049-2084)
-        u64 bits = 0;
-#pragma unroll
-        for (int s = 0; s < 16; s++)
-        {
-            const int px = ((s & 3) << 2) | (s >> 2); // s-th emitted = pixel with selectorOrder[px] == s
-            const u32 code = px < 8 ? (bestIdxLo >> (3 * px)) & 7u : (bestIdxHi >> (3 * (px - 8))) & 7u;
-            bits = (bits << 3) | code;
-        }
-        uint8_t *o = out + (size_t)blockIndex * A.outStride + A.outOffset;
-        const u32 w0 = ((u32)bestBase & 0xffu) | ((u32)(((bestMultiplier << 4) | bestTable) & 0xff) << 8) | ((u32)((bits >> 40) & 0xff) << 16) | ((u32)((bits >> 32) & 0xff) << 24);
-        const u32 w1 = bswap32((u32)bits);
-        uint2 v;
-        v.x = w0;
-        v.y = w1;
-        *reinterpret_cast<uint2 *>(o) = v;
-    }
-}
-
-// Launches of at most this many blocks use the sixteen-lanes-per-block form of the EAC search: the chip is not full there
-// (256 CUs x 4 SIMDs x 4 waves x 64 lanes = 262 144 blocks resident in the one-lane form), so latency is what counts.
-static const uint32_t kEacSpreadMax = 65536u;
+#include "eac_alpha_kernel.h"
 
 extern "C" hipError_t cvttmi_launch_etc2(const void *d_blocks, void *d_out, const CvttEtcArgs *args,
                                          const CvttDeviceTables *d_tables, int mode, hipStream_t stream)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Exhaustive check (CPU, numpy) that the integer form of the BC6H endpoint quantisation in csrc/bc6h_kernel.hip equals the
+"""Exhaustive check (CPU, numpy) that the integer form of the BC6H endpoint quantisation in csrc/bc6h_quant.h equals the
 reference's binary32 sequence (QuantizeSingleEndpointElementUnsigned / Signed, BC67.cpp:2425-2445: a division rounded up,
 a subtraction, a ceiling, a clamp) for every colour-space value the clamp lets through, and that the v_mul_hi_u32 constant
 divides exactly.   python tools/check_bc6h_quantize.py"""
