@@ -7,6 +7,7 @@ own pinned staging.  There is no CPU fallback: if the HIP library cannot be load
 gfx950 device is present every encode raises ``CvttError``.
 """
 import ctypes
+import functools
 import os
 import sys
 
@@ -201,6 +202,7 @@ _EXPORTS = (
     "cvttmi_mip_level_count", "cvttmi_mip_layout", "cvttmi_build_mips_device",
     "cvttmi_decode_image_device", "cvttmi_decode_mips_device",
     "cvttmi_build_mips_filtered_device", "cvttmi_srgb_tables",
+    "cvttmi_texture_layout", "cvttmi_texture_subresource", "cvttmi_build_mips_array_device", "cvttmi_encode_texture_device",
 )
 
 _lib = None
@@ -294,6 +296,11 @@ def load_library():
                                                       ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.c_void_p]
     lib.cvttmi_srgb_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    U = ctypes.c_uint32
+    lib.cvttmi_texture_layout.argtypes = [U, U, I, U, U, U, I, P]
+    lib.cvttmi_texture_subresource.argtypes = [U, U, I, U, U, U, I, U, U, ctypes.POINTER(N), ctypes.POINTER(N)]
+    lib.cvttmi_build_mips_array_device.argtypes = [P, P, N, P, U, U, N, N, I, U, U, U, P]
+    lib.cvttmi_encode_texture_device.argtypes = [P, I, P, N, P, U, U, N, N, U, U, U, I, P, P, P, P, N, P]
     lib.cvttmi_decode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
@@ -426,6 +433,91 @@ def mip_layout(width, height, pixel_bytes, bytes_per_block, levels=None):
     end = table[levels]
     out.pyramid_bytes, out.tile_count, out.block_count = int(end.byteOffset), int(end.firstTile), int(end.firstBlock)
     return out
+
+
+# texture arrays and cube maps (include/cvtt_mi355x.h CVTTMI_ORDER_*): the packed output's order and its names
+ORDER_LAYER_MAJOR, ORDER_LEVEL_MAJOR = 0, 1
+ORDERS = {"layer": ORDER_LAYER_MAJOR, "level": ORDER_LEVEL_MAJOR}
+
+
+def order_value(order):
+    """"layer" (DDS order) / "level" (KTX order), or an ORDER_* value -> the value the library takes (unknown integers are the
+    library's to refuse)"""
+    if isinstance(order, str):
+        if order not in ORDERS:
+            raise CvttError("unknown order %r (one of %s)" % (order, ", ".join(ORDERS)))
+        return ORDERS[order]
+    if isinstance(order, bool) or not isinstance(order, int) or not -(1 << 31) <= order < (1 << 31):
+        raise CvttError("order must be a name or an ORDER_* value, got %r" % (order,))
+    return order
+
+
+class TextureSizes(ctypes.Structure):
+    """byte image of cvttmi_texture_sizes: what cvttmi_texture_layout reports for `layers` images with `levels` levels each"""
+    _fields_ = [("pyramidLayerBytes", ctypes.c_size_t), ("pyramidBytes", ctypes.c_size_t), ("tilesPerLayer", ctypes.c_size_t),
+                ("tiles", ctypes.c_size_t), ("blocksPerLayer", ctypes.c_size_t), ("blocks", ctypes.c_size_t), ("workBytes", ctypes.c_size_t)]
+
+
+def _pixel_kind(pixel_bytes):
+    return {4: PIXELS_RGBA8, 8: PIXELS_RGBA16F}.get(pixel_bytes, -1)
+
+
+def _u32(value, what):
+    value = int(value)
+    if not 0 <= value <= 0xFFFFFFFF:
+        raise CvttError("%s = %d is no uint32" % (what, value))
+    return value
+
+
+def texture_layout(width, height, pixel_bytes, bytes_per_block, levels=None, layers=1, order="layer"):
+    """cvttmi_texture_layout: the sizes of a texture of `layers` images of `pixel_bytes` per texel (4 = RGBA8, 8 = RGBA16F), each
+    with `levels` levels (None = the full chain), for a format of `bytes_per_block` -> TextureSizes.  Needs no device."""
+    levels = mip_level_count(width, height) if levels is None else levels
+    out = TextureSizes()
+    rc = load_library().cvttmi_texture_layout(_u32(width, "width"), _u32(height, "height"), _pixel_kind(pixel_bytes), _u32(bytes_per_block, "bytes_per_block"),
+                                              _u32(levels, "levels"), _u32(layers, "layers"), order_value(order), ctypes.byref(out))
+    if rc != 0:
+        raise CvttError("cvttmi_texture_layout(%d x %d, %d bytes per texel, %d bytes per block, %d levels, %d layers, order %r) failed (%d)"
+                        % (width, height, pixel_bytes, bytes_per_block, levels, layers, order, rc))
+    return out
+
+
+def texture_subresource(width, height, pixel_bytes, bytes_per_block, levels, layers, order, layer, level):
+    """cvttmi_texture_subresource: (first block, block count) of (layer, level) in the packed output of a texture in `order`.
+    levels: None = the full chain.  Needs no device."""
+    levels = mip_level_count(width, height) if levels is None else levels
+    first, count = ctypes.c_size_t(), ctypes.c_size_t()
+    rc = load_library().cvttmi_texture_subresource(_u32(width, "width"), _u32(height, "height"), _pixel_kind(pixel_bytes),
+                                                   _u32(bytes_per_block, "bytes_per_block"), _u32(levels, "levels"), _u32(layers, "layers"),
+                                                   order_value(order), _u32(layer, "layer"), _u32(level, "level"), ctypes.byref(first), ctypes.byref(count))
+    if rc != 0:
+        raise CvttError("cvttmi_texture_subresource(%d x %d, %d levels, %d layers, order %r, layer %d, level %d) failed (%d)"
+                        % (width, height, levels, layers, order, layer, level, rc))
+    return int(first.value), int(count.value)
+
+
+@functools.lru_cache(maxsize=64)
+def _texture_places(width, height, pixel_bytes, bytes_per_block, levels, layers, order):
+    """texture_subresource of every subresource, kept for the shapes last used, as (first block of layer 0, blocks from one layer
+    to the next, block count) per level: in both orders a level's layers are evenly spaced, which is checked here, not assumed"""
+    places = [[texture_subresource(width, height, pixel_bytes, bytes_per_block, levels, layers, order, layer, level)
+               for level in range(levels)] for layer in range(layers)]
+    out = []
+    for level in range(levels):
+        first, count = places[0][level]
+        step = places[1][level][0] - first if layers > 1 else count
+        if any(places[layer][level] != (first + layer * step, count) for layer in range(layers)) or step < count:
+            raise CvttError("cvttmi_texture_subresource: the layers of level %d are not evenly spaced" % level)
+        out.append((first, step, count))
+    return tuple(out)
+
+
+class TextureBlocks(list):
+    """What Context.encode_texture returns: [layer][level] -> the (blocks, bytes per block) uint8 view of that subresource.
+    base: the ONE allocation all of them are views of, (all blocks, bytes per block), in `order` -- what a container of that
+    order stores behind its header."""
+    base = None
+    order = "layer"
 
 
 class ErrorTotals(ctypes.Structure):
@@ -965,6 +1057,94 @@ class Context:
             self._check(self._lib.cvttmi_compact_rows_device(self._h, out[L.firstBlock:].data_ptr(), packed[L.firstTile:].data_ptr(),
                                                              L.width, L.height, bpb, sp), "compact_rows")
         return [out[L.firstBlock: L.firstBlock + L.blockCount] for L in layout]
+
+    # -- texture arrays and cube maps: `layers` images of one size through mips and encode at once (cvtt_mi355x.h) --
+    def _images_in(self, images):
+        """the (L, H, W, 4) images of build_mips_array / encode_texture, texels contiguous (rows and layers may be strided);
+        a list of (H, W, 4) tensors is stacked once -> (tensor, row pitch in bytes, layer pitch in bytes)"""
+        import torch
+        if isinstance(images, (list, tuple)):
+            images = [self._image_in(t) for t in images]
+            if not images or any(t.shape != images[0].shape or t.dtype != images[0].dtype for t in images):
+                raise CvttError("images must be a non-empty list of (H, W, 4) tensors of one size and dtype")
+            images = torch.stack(images)
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dim() == 4 and images.shape[3] == 4 and images.shape[0] >= 1
+                and images.shape[1] >= 1 and images.shape[2] >= 1):
+            raise CvttError("images must be a CUDA tensor of shape (L, H, W, 4) or a list of (H, W, 4) CUDA tensors")
+        if images.device.index != self.device:
+            raise CvttError("images live on cuda:%d but this context was created for cuda:%d" % (images.device.index, self.device))
+        if images.element_size() not in (1, 2):
+            raise CvttError("images must be RGBA8 or RGBA16F")
+        n, h, w = (int(v) for v in images.shape[:3])
+        # a stride of a dimension of size 1 says nothing: such a pitch is the tight one
+        row = images.stride(1) if h > 1 else 4 * w
+        layer = images.stride(0) if n > 1 else h * row
+        if not (images.stride(3) == 1 and images.stride(2) == 4 and row >= 4 * w and row % 4 == 0 and layer >= h * row and layer % 4 == 0):
+            images = images.contiguous()
+            row, layer = 4 * w, 4 * w * h
+        esz = images.element_size()
+        return images, row * esz, layer * esz
+
+    def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box"):
+        """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): build_mips
+        for every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
+        into one allocation: layer l's chain as mip_layout places it, texture_layout's pyramidLayerBytes apart.  levels, signed,
+        filter: as for build_mips."""
+        import torch
+        images, row_pitch, layer_pitch = self._images_in(images)
+        n, h, w = (int(v) for v in images.shape[:3])
+        esz = images.element_size()
+        if esz == 2 and signed:
+            raise CvttError("signed selects the int8 rule of an RGBA8 image")
+        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+        layout = mip_layout(w, h, 4 * esz, 16, levels)
+        sizes = texture_layout(w, h, 4 * esz, 16, len(layout), n)
+        pyramids = torch.empty(sizes.pyramidBytes, dtype=torch.uint8, device=images.device)
+        self._check(self._lib.cvttmi_build_mips_array_device(self._h, pyramids.data_ptr(), sizes.pyramidBytes, images.data_ptr(), w, h, row_pitch,
+                                                             layer_pitch, kind, len(layout), n, mip_filter_value(filter),
+                                                             ctypes.c_void_p(self._stream(stream, images.device))), "build_mips_array")
+        # one strided view per level over all layers, then its n slices (pyramidLayerBytes is a multiple of 256: whole elements)
+        typed = pyramids.view(images.dtype)
+        per_level = [images.unbind(0)] + [typed.as_strided((n, L.height, L.width, 4), (sizes.pyramidLayerBytes // esz, 4 * L.width, 4, 1),
+                                                           L.byteOffset // esz).unbind(0) for L in layout[1:]]
+        return [[views[l] for views in per_level] for l in range(n)]
+
+    def encode_texture(self, fmt, images, options=None, plan=None, levels=None, order="layer", mip_filter="box", stream=None):
+        """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones): the layers of a texture array, or the 6 n faces of a cube (array)
+        in the order +X -X +Y -Y +Z -Z -> TextureBlocks: [layer][level] packed blocks, uint8 views into ONE allocation (.base) in
+        `order`: "layer" = every layer's chain consecutive (DDS), "level" = every level's layers consecutive (KTX).  One C call
+        (cvttmi_encode_texture_device): the mips of all layers a launch per level, one tile launch, one search, one compact launch.
+        [l][L] equals encode_mips(fmt, images[l], ..)[L] byte for byte.  fmt, levels, mip_filter: as for encode_mips."""
+        import torch
+        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
+            raise CvttError("unknown format %r" % (fmt,))
+        fid, bpb, _, _ = TEXTURE_FORMATS[fmt]
+        images, row_pitch, layer_pitch = self._images_in(images)
+        n, h, w = (int(v) for v in images.shape[:3])
+        esz = images.element_size()
+        if (esz == 2) != (fmt in ("bc6hu", "bc6hs")):
+            raise CvttError("%s is encoded from %s images" % (fmt, "RGBA16F" if esz == 1 else "RGBA8"))
+        options = options if options is not None else Options()
+        if fmt == "bc7" and plan is None:
+            plan = BC7EncodingPlan()
+        levels = mip_level_count(w, h) if levels is None else int(levels)
+        ov = order_value(order)
+        sizes = texture_layout(w, h, 4 * esz, bpb, levels, n, ov)
+        out = torch.empty((sizes.blocks, bpb), dtype=torch.uint8, device=images.device)
+        work = torch.empty(sizes.workBytes, dtype=torch.uint8, device=images.device)
+        self._check(self._lib.cvttmi_encode_texture_device(self._h, fid, out.data_ptr(), sizes.blocks * bpb, images.data_ptr(), w, h, row_pitch,
+                                                           layer_pitch, n, levels, mip_filter_value(mip_filter), ov, ctypes.addressof(options),
+                                                           ctypes.addressof(plan) if plan is not None else None, None, work.data_ptr(),
+                                                           sizes.workBytes, ctypes.c_void_p(self._stream(stream, images.device))),
+                    "encode_texture(%s)" % fmt)
+        res = TextureBlocks()
+        res.base, res.order = out, "level" if ov == ORDER_LEVEL_MAJOR else "layer"
+        res.work = work  # kept as long as the result: on a caller's own stream the kernels may still be using it
+        # one strided view per level over all layers, then its n slices: a few tensor operations per level, not per subresource
+        per_level = [out.as_strided((n, count, bpb), (step * bpb, bpb, 1), first * bpb).unbind(0)
+                     for first, step, count in _texture_places(w, h, 4 * esz, bpb, levels, n, ov)]
+        res.extend([views[l] for views in per_level] for l in range(n))
+        return res
 
 
     # -- packed blocks -> linear images on the device (cvtt_mi355x.h, "decoding into images") --

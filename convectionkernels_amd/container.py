@@ -256,3 +256,132 @@ def read_dds_mips(path_or_bytes):
         levels.append(np.frombuffer(raw, np.uint8, n * per, off).reshape(n, per).copy())
         off += n * per
     return name, width, height, levels
+
+
+# ---- texture arrays and cube maps: `layers` = [layer][level] packed blocks (what Context.encode_texture returns), layer =
+# array element x faces + face, the faces of a cube in the order +X -X +Y -Y +Z -Z.  KTX stores level-major (every level's
+# layers consecutive), DDS layer-major (every layer's chain consecutive): encode_texture's order="level" / "layer". ----
+
+def _texture_payloads(fmt, width, height, layers, cube):
+    """[layer][level] -> the same as checked uint8 byte arrays.  ValueError: no layers, a cube that is not square or whose layers
+    are no multiple of 6, layers of unequal level counts, a wrong block count in any (layer, level)."""
+    base = getattr(layers, "base", None)
+    layers = [list(levels) for levels in layers]
+    if not layers:
+        raise ValueError("a texture has at least one layer")
+    if cube and (width != height or len(layers) % 6 != 0):
+        raise ValueError("a cube needs square faces and 6 n layers, got %dx%d and %d layer(s)" % (width, height, len(layers)))
+    if any(len(levels) != len(layers[0]) for levels in layers):
+        raise ValueError("every layer needs the same number of mip levels, got %s" % sorted({len(levels) for levels in layers}))
+    if base is not None and hasattr(base, "data_ptr"):
+        # the views of one device allocation: one copy to the host, the same views of that copy
+        host, start, per = base.detach().cpu().numpy().reshape(-1), base.data_ptr(), FORMATS[fmt][0]
+        layers = [[host[t.data_ptr() - start: t.data_ptr() - start + t.shape[0] * per] for t in levels] for levels in layers]
+    return [_mip_payloads(fmt, width, height, levels) for levels in layers]
+
+
+def ktx_texture_bytes(fmt, width, height, layers, cube=False, srgb=False):
+    """KTX 1.1 of a 2-D texture, a texture array, a cube or a cube array.  numberOfFaces = 6 for cubes, else 1;
+    numberOfArrayElements = 0 for a single texture or a single cube, else the element count (cubes, for a cube array).  Per level
+    one uint32 imageSize, then the level of every element, inside an element of every face.  imageSize is the bytes of ONE FACE for
+    a non-array cube (KTX 1 specification, 2.16) and of the whole level in every other case.  Blocks are 8 or 16 bytes, so cube and
+    mip padding are always empty.  One layer, not a cube: the bytes of ktx_mips_bytes.  srgb: as for ktx_bytes."""
+    fmt = canonical(fmt)
+    internal, base = _codes(fmt, srgb)[0], FORMATS[fmt][2]
+    data = _texture_payloads(fmt, width, height, layers, cube)
+    faces = 6 if cube else 1
+    elements = len(data) // faces
+    header = _KTX_ID + struct.pack("<13I", 0x04030201, 0, 1, 0, internal, base, width, height, 0, 0 if elements == 1 else elements, faces,
+                                   len(data[0]), 0)
+    out = [header]
+    for level in range(len(data[0])):
+        one = data[0][level].size
+        out.append(struct.pack("<I", one if cube and elements == 1 else one * len(data)))
+        out.extend(d[level].tobytes() for d in data)
+    return b"".join(out)
+
+
+def write_ktx_texture(path, fmt, width, height, layers, cube=False, srgb=False):
+    with open(path, "wb") as f:
+        f.write(ktx_texture_bytes(fmt, width, height, layers, cube, srgb))
+
+
+def read_ktx_texture(path_or_bytes):
+    """-> (format name, width, height, layers[layer][level] blocks (N, bytesPerBlock) uint8, cube); every file ktx_bytes and
+    ktx_mips_bytes write reads as one layer"""
+    raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+    name, width, height, _ = read_ktx(raw)
+    elements, faces, count, kv = struct.unpack_from("<4I", raw, 12 + 4 * 9)
+    if faces not in (1, 6):
+        raise ValueError("numberOfFaces is %d" % faces)
+    cube = faces == 6
+    n = max(1, elements) * faces
+    per = FORMATS[name][0]
+    off, layers = 64 + kv, [[] for _ in range(n)]
+    for level, (w, h) in enumerate(mip_sizes(width, height, max(1, count))):
+        size, = struct.unpack_from("<I", raw, off)
+        one = ((w + 3) // 4) * ((h + 3) // 4) * per
+        if size != (one if cube and elements == 0 else one * n):
+            raise ValueError("mip level %d (%dx%d, %d layer(s)) holds %d bytes" % (level, w, h, n, size))
+        off += 4
+        if off + one * n > len(raw):
+            raise ValueError("mip level %d (%dx%d) is cut short" % (level, w, h))
+        for layer in range(n):
+            layers[layer].append(np.frombuffer(raw, np.uint8, one, off).reshape(-1, per).copy())
+            off += one
+    return name, width, height, layers, cube
+
+
+def dds_texture_bytes(fmt, width, height, layers, cube=False, srgb=False):
+    """DDS (DX10 header) of a 2-D texture, a texture array, a cube or a cube array: arraySize = the elements (cubes, for a cube
+    file), miscFlag = 0x4 (DDS_RESOURCE_MISC_TEXTURECUBE) for cubes, which also set DDSCAPS_COMPLEX and dwCaps2 = DDSCAPS2_CUBEMAP
+    with all six face bits (0xFE00).  The payload is layer-major: every layer's chain, level 0 first; the mip fields are those of
+    dds_mips_bytes.  One layer, not a cube: the bytes of dds_mips_bytes.  srgb: as for ktx_bytes."""
+    fmt = canonical(fmt)
+    if FORMATS[fmt][3] is None:
+        raise ValueError("%s has no DXGI format; use KTX" % fmt)
+    dxgi = _codes(fmt, srgb)[1]
+    data = _texture_payloads(fmt, width, height, layers, cube)
+    flags = 0x1 | 0x2 | 0x4 | 0x1000 | 0x80000  # DDSD_CAPS | HEIGHT | WIDTH | PIXELFORMAT | LINEARSIZE
+    caps, caps2 = 0x1000, 0  # DDSCAPS_TEXTURE
+    if len(data[0]) > 1:
+        flags |= 0x20000  # DDSD_MIPMAPCOUNT
+        caps |= 0x8 | 0x400000  # DDSCAPS_COMPLEX | DDSCAPS_MIPMAP
+    if cube:
+        caps |= 0x8
+        caps2 = 0xFE00  # DDSCAPS2_CUBEMAP | the six DDSCAPS2_CUBEMAP_*
+    pixel_format = struct.pack("<2I4s5I", 32, 0x4, b"DX10", 0, 0, 0, 0, 0)  # DDPF_FOURCC
+    header = struct.pack("<7I", 124, flags, height, width, data[0][0].size, 0, len(data[0])) + bytes(44) + pixel_format + \
+        struct.pack("<5I", caps, caps2, 0, 0, 0)
+    dx10 = struct.pack("<5I", dxgi, 3, 0x4 if cube else 0, len(data) // (6 if cube else 1), 0)  # D3D10_RESOURCE_DIMENSION_TEXTURE2D
+    return _DDS_MAGIC + header + dx10 + b"".join(d.tobytes() for levels in data for d in levels)
+
+
+def write_dds_texture(path, fmt, width, height, layers, cube=False, srgb=False):
+    with open(path, "wb") as f:
+        f.write(dds_texture_bytes(fmt, width, height, layers, cube, srgb))
+
+
+def read_dds_texture(path_or_bytes):
+    """-> (format name, width, height, layers[layer][level] blocks, cube); every file dds_bytes and dds_mips_bytes write reads as
+    one layer"""
+    raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+    name, width, height, _ = read_dds(raw)
+    flags, = struct.unpack_from("<I", raw, 8)
+    count, = struct.unpack_from("<I", raw, 28)
+    misc, elements = struct.unpack_from("<2I", raw, 136)
+    cube = bool(misc & 0x4)
+    n = max(1, elements) * (6 if cube else 1)
+    per = FORMATS[name][0]
+    off, layers = 148, []
+    sizes = mip_sizes(width, height, max(1, count) if flags & 0x20000 else 1)
+    for layer in range(n):
+        levels = []
+        for level, (w, h) in enumerate(sizes):
+            blocks = ((w + 3) // 4) * ((h + 3) // 4)
+            if off + blocks * per > len(raw):
+                raise ValueError("layer %d, mip level %d (%dx%d) is cut short" % (layer, level, w, h))
+            levels.append(np.frombuffer(raw, np.uint8, blocks * per, off).reshape(blocks, per).copy())
+            off += blocks * per
+        layers.append(levels)
+    return name, width, height, layers, cube

@@ -171,4 +171,28 @@ struct CvttDecodeLevels
     uint32_t numBlocks; // of all levels
 };
 
+// A texture = `layers` images of one size with `count` levels each (cvttmi_encode_texture_device), for the chain tile and
+// the chain compact kernels of texture_kernel.hip.  Per level: where layer 0's texels are (level 0: the caller's images, the
+// others: the pyramids) and how far the next layer's are; its tiles inside one layer's part of the PixelBlock buffer
+// ([firstTile, firstTile + tileCount), tilesPerRow = ceil(ceil(width / 4) / 8) * 8 a block row) and its blocks inside one
+// layer's part of the packed output ([firstBlock, firstBlock + blockCount), blocksPerRow = ceil(width / 4) a row).  A layer's
+// tiles are consecutive: layer l's start at l * tilesPerLayer.  The whole table travels as a kernel argument.
+struct CvttTextureLevel
+{
+    const uint8_t *image;
+    size_t pitch;       // bytes between texel rows
+    size_t layerStride; // bytes between the same level of consecutive layers
+    uint32_t width, height;
+    uint32_t firstTile, tilesPerRow;
+    uint32_t firstBlock, blockCount, blocksPerRow;
+    uint32_t pad;
+};
+struct CvttTextureLevels
+{
+    CvttTextureLevel level[kCvttDecodeLevels];
+    uint32_t count, layers;
+    uint32_t tilesPerLayer, blocksPerLayer;
+    uint32_t levelMajor; // the packed output's order: 0 = every layer's chain consecutive, 1 = every level's layers consecutive
+};
+
 #endif

@@ -29,8 +29,24 @@ __device__ __forceinline__ uint32_t box4x8(uint32_t a, uint32_t b, uint32_t c, u
     return (((even >> 2) & m) | (((odd >> 2) & m) << 8)) ^ bias;
 }
 
+// What one level's launch reads and writes: one image (layers == 0), or the same level of `layers` images of a texture array,
+// srcLayer / dstLayer bytes apart, layer z in workgroups z of the grid.
+struct MipLayers
+{
+    const void *src;
+    size_t srcPitch;
+    void *dst;
+    size_t dstPitch;
+    uint32_t srcW, srcH;
+    size_t srcLayer, dstLayer;
+    uint32_t layers;
+};
+const uint32_t kMipMaxLayers = 65535; // the z limit of a grid
+
 // One level's launch.  The wide kernel (16 bytes of output per lane) runs when both row starts, both pitches and the output
-// width allow 16-byte accesses and no coordinate needs a clamp; everything else takes the narrow one, a texel per lane.
+// width allow 16-byte accesses and no coordinate needs a clamp -- for every layer: the two layer strides enter the same test
+// (with the first layer's rows and both strides on 16-byte boundaries every layer's rows are); everything else takes the
+// narrow one, a texel per lane.
 struct MipLaunch
 {
     bool wide;
@@ -38,14 +54,16 @@ struct MipLaunch
     dim3 grid, block;
 };
 
-inline MipLaunch mipLaunchShape(const void *d_src, size_t srcPitch, const void *d_dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
-                                uint32_t texel)
+inline MipLaunch mipLaunchShape(const MipLayers &m, uint32_t texel)
 {
+    const uint32_t srcW = m.srcW, srcH = m.srcH;
     MipLaunch L;
     L.dstW = srcW > 1u ? srcW >> 1 : 1u;
     L.dstH = srcH > 1u ? srcH >> 1 : 1u;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | srcPitch | dstPitch |
-                           ((uintptr_t)L.dstW * texel);
+    uintptr_t bits = reinterpret_cast<uintptr_t>(m.src) | reinterpret_cast<uintptr_t>(m.dst) | m.srcPitch | m.dstPitch |
+                     ((uintptr_t)L.dstW * texel);
+    if (m.layers > 1u)
+        bits |= m.srcLayer | m.dstLayer;
     L.wide = (bits & 15u) == 0 && srcW >= 2u && srcH >= 2u;
     L.perRow = L.wide ? L.dstW / (16u / texel) : L.dstW;
     // a workgroup of 256 lanes, as wide as the row needs (a power of two) and as many rows high as that leaves; at most 1024
@@ -56,7 +74,7 @@ inline MipLaunch mipLaunchShape(const void *d_src, size_t srcPitch, const void *
     const uint32_t by = 256u / bx;
     const uint32_t gy = (L.dstH + by - 1u) / by;
     L.block = dim3(bx, by);
-    L.grid = dim3((L.perRow + bx - 1u) / bx, gy < 1024u ? gy : 1024u);
+    L.grid = dim3((L.perRow + bx - 1u) / bx, gy < 1024u ? gy : 1024u, m.layers ? m.layers : 1u);
     return L;
 }
 } // namespace

@@ -43,11 +43,18 @@ __device__ __forceinline__ uint32_t boxWord(uint32_t a, uint32_t b, uint32_t c, 
 }
 
 // One output texel per lane.  Texel = uint32_t (RGBA8) or uint2 (RGBA16F).
-template <int KIND>
+// LAYERED (here and in the wide kernel): workgroup z takes layer z of a texture array, `srcLayer` / `dstLayer` bytes further on.
+template <int KIND, bool LAYERED>
 __global__ void __launch_bounds__(256) cvttmi_downsample_narrow_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                         uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW,
-                                                                        uint32_t srcH, uint32_t dstW, uint32_t dstH)
+                                                                        uint32_t srcH, uint32_t dstW, uint32_t dstH, size_t srcLayer,
+                                                                        size_t dstLayer)
 {
+    if (LAYERED)
+    {
+        src += blockIdx.z * srcLayer;
+        dst += blockIdx.z * dstLayer;
+    }
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= dstW)
         return;
@@ -75,11 +82,16 @@ __global__ void __launch_bounds__(256) cvttmi_downsample_narrow_kernel(const uin
 // 16 bytes of output per lane: chunk `i` of a row is output bytes [16 i, 16 i + 16) from input bytes [32 i, 32 i + 32) of
 // rows 2y and 2y + 1.  chunks = dstW * texel bytes / 16, exact; the input rows hold at least 2 * dstW texels, so no clamp
 // in x, and the launcher sends srcH == 1 to the narrow kernel, so none in y.
-template <int KIND>
+template <int KIND, bool LAYERED>
 __global__ void __launch_bounds__(256) cvttmi_downsample_wide_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                       uint8_t *__restrict__ dst, size_t dstPitch, uint32_t chunks,
-                                                                      uint32_t dstH)
+                                                                      uint32_t dstH, size_t srcLayer, size_t dstLayer)
 {
+    if (LAYERED)
+    {
+        src += blockIdx.z * srcLayer;
+        dst += blockIdx.z * dstLayer;
+    }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= chunks)
         return;
@@ -109,18 +121,33 @@ __global__ void __launch_bounds__(256) cvttmi_downsample_wide_kernel(const uint8
     }
 }
 
-template <int KIND>
-hipError_t launchDownsample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
-                            hipStream_t stream)
+// layers == 0: one image (the instances without LAYERED, as before texture arrays existed); otherwise `layers` (at most the z
+// limit of a grid: the caller cuts longer arrays) images `srcLayer` / `dstLayer` bytes apart, one launch for all of them
+template <int KIND, bool LAYERED>
+hipError_t launchDownsample(const MipLayers &m, hipStream_t stream)
 {
-    const MipLaunch L = mipLaunchShape(d_src, srcPitch, d_dst, dstPitch, srcW, srcH, KIND == kRGBA16F ? 8u : 4u);
+    const MipLaunch L = mipLaunchShape(m, KIND == kRGBA16F ? 8u : 4u);
     if (L.wide)
-        hipLaunchKernelGGL(cvttmi_downsample_wide_kernel<KIND>, L.grid, L.block, 0, stream, (const uint8_t *)d_src, srcPitch,
-                           (uint8_t *)d_dst, dstPitch, L.perRow, L.dstH);
+        hipLaunchKernelGGL((cvttmi_downsample_wide_kernel<KIND, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
+                           (uint8_t *)m.dst, m.dstPitch, L.perRow, L.dstH, m.srcLayer, m.dstLayer);
     else
-        hipLaunchKernelGGL(cvttmi_downsample_narrow_kernel<KIND>, L.grid, L.block, 0, stream, (const uint8_t *)d_src, srcPitch,
-                           (uint8_t *)d_dst, dstPitch, srcW, srcH, L.dstW, L.dstH);
+        hipLaunchKernelGGL((cvttmi_downsample_narrow_kernel<KIND, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
+                           (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, L.dstW, L.dstH, m.srcLayer, m.dstLayer);
     return hipGetLastError();
+}
+
+template <bool LAYERED>
+hipError_t downsampleByKind(const MipLayers &m, int kind, hipStream_t stream)
+{
+    if (m.srcW == 0 || m.srcH == 0)
+        return hipSuccess;
+    switch (kind)
+    {
+    case kRGBA8: return launchDownsample<kRGBA8, LAYERED>(m, stream);
+    case kRGBA16F: return launchDownsample<kRGBA16F, LAYERED>(m, stream);
+    case kRGBA8Snorm: return launchDownsample<kRGBA8Snorm, LAYERED>(m, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 } // namespace
 
@@ -129,13 +156,15 @@ hipError_t launchDownsample(const void *d_src, size_t srcPitch, void *d_dst, siz
 extern "C" hipError_t cvttmi_launch_downsample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW,
                                                uint32_t srcH, int kind, hipStream_t stream)
 {
-    if (srcW == 0 || srcH == 0)
-        return hipSuccess;
-    switch (kind)
-    {
-    case kRGBA8: return launchDownsample<kRGBA8>(d_src, srcPitch, d_dst, dstPitch, srcW, srcH, stream);
-    case kRGBA16F: return launchDownsample<kRGBA16F>(d_src, srcPitch, d_dst, dstPitch, srcW, srcH, stream);
-    case kRGBA8Snorm: return launchDownsample<kRGBA8Snorm>(d_src, srcPitch, d_dst, dstPitch, srcW, srcH, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return downsampleByKind<false>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, 0, 0, 0}, kind, stream);
+}
+
+// ... of `layers` images (1 .. 65535) at once: layer z reads d_src + z * srcLayer and writes d_dst + z * dstLayer
+extern "C" hipError_t cvttmi_launch_downsample_layered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
+                                                       size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind,
+                                                       hipStream_t stream)
+{
+    if (layers == 0 || layers > kMipMaxLayers)
+        return hipErrorInvalidValue;
+    return downsampleByKind<true>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, stream);
 }

@@ -1,6 +1,6 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-alphaweight] [-srgb] [-metrics] input output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-alphaweight] [-srgb] [-metrics] [-array | -cube] input [input ...] output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
@@ -16,7 +16,12 @@ unchanged, then one line per further level: its PSNR over the format's channels 
 R11, which has no image form.
 -mipfilter box|srgb|normal, -alphaweight: the filter of the chain (Context.build_mips: "srgb" averages colour in linear light,
 "normal" renormalises a normal map, -alphaweight weights colour by alpha -- with box or srgb); either implies -mips.
--srgb: the file carries the sRGB code of its format (container.SRGB_FORMATS).  Only a mark: level 0 and the encode are unchanged."""
+-srgb: the file carries the sRGB code of its format (container.SRGB_FORMATS).  Only a mark: level 0 and the encode are unchanged.
+-array: every input is one layer of a texture array (N inputs, then the output); -cube: the inputs are the faces of a cube in the
+order +X -X +Y -Y +Z -Z, or of a cube array (6 n inputs).  Either also takes a single .npy of shape (L, H, W, 4).  All layers
+must be of one size, a cube's faces square.  The layers go through one call (Context.encode_texture) and into one KTX (level-major)
+or, with -dds, DDS (layer-major) file that a loader binds as an array or a cube; combines with -mips, -mipfilter, -alphaweight,
+-srgb and -quality.  With -metrics the lines above are printed for every layer under a `layer N` heading.  Not for R11."""
 import sys
 
 import numpy as np
@@ -110,6 +115,34 @@ def measure_file(image, fmt, packed, options=None, ctx=None):
     return ctx.measure_image(fmt, dev, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
 
 
+def load_layers(paths):
+    """the inputs of -array / -cube -> (L, H, W, 4) uint8: one image per path, or a single .npy of that shape"""
+    if len(paths) == 1 and paths[0].endswith(".npy"):
+        stack = np.load(paths[0])
+        if stack.ndim == 4:
+            if stack.shape[0] < 1 or stack.shape[3] != 4 or stack.dtype != np.uint8:
+                raise ValueError("expected an (L, H, W, 4) uint8 array, got %s %s" % (stack.shape, stack.dtype))
+            return np.ascontiguousarray(stack)
+    images = [load_rgba8(p) for p in paths]
+    for p, img in zip(paths, images):
+        if img.shape != images[0].shape:
+            raise ValueError("all layers must be of one size: %s is %dx%d, %s is %dx%d"
+                             % (paths[0], images[0].shape[1], images[0].shape[0], p, img.shape[1], img.shape[0]))
+    return np.stack(images)
+
+
+def encode_file_texture(images, fmt, options=None, plan=None, ctx=None, mips=False, mip_filter="box", order="level"):
+    """(L, H, W, 4) uint8 numpy layers -> [layer][level] packed blocks (numpy), one level or the full chain (not R11)"""
+    import torch
+    ctx = ctx or api.default_context()
+    blocks = ctx.encode_texture(container.canonical(fmt), torch.from_numpy(images).cuda(ctx.device), options, plan,
+                                levels=None if mips else 1, order=order, mip_filter=mip_filter)
+    torch.cuda.synchronize(ctx.device)
+    host, start = blocks.base.cpu().numpy(), blocks.base.data_ptr()
+    per = host.shape[1]
+    return [[host[(t.data_ptr() - start) // per: (t.data_ptr() - start) // per + t.shape[0]] for t in levels] for levels in blocks]
+
+
 def print_metrics(report, out=None):
     out = out or sys.stdout
     for c, name in enumerate("RGBA"):
@@ -118,10 +151,18 @@ def print_metrics(report, out=None):
     out.write("psnr %.4f dB (%s, %d texels)\n" % (report.psnr(), report.channels.upper(), report.texels))
 
 
+def print_mip_metrics(reports, w, h, out=None):
+    """one line per level 1 .. of a w x h image: the reports measure_file_mips returned"""
+    out = out or sys.stdout
+    for l, report in enumerate(reports, 1):
+        out.write("mip %d %dx%d psnr %.4f dB (%s, %d texels)\n" % (l, max(1, w >> l), max(1, h >> l), report.psnr(),
+                                                                  report.channels.upper(), report.texels))
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     fmt, uniform, fake, quality, dds, metrics, mips, paths = "etc2rgb", False, False, None, False, False, False, []
-    mip_filter, alpha_weight, srgb = None, False, False
+    mip_filter, alpha_weight, srgb, array, cube = None, False, False, False, False
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -148,13 +189,17 @@ def main(argv=None):
             srgb = True
         elif a == "-fakebt709":
             fake = True
+        elif a == "-array":
+            array = True
+        elif a == "-cube":
+            cube = True
         elif a.startswith("-"):
             sys.stderr.write(USAGE + "\n")
             return 2
         else:
             paths.append(a)
         i += 1
-    if len(paths) != 2:
+    if (array and cube) or len(paths) < 2 or (len(paths) != 2 and not (array or cube)):
         sys.stderr.write(USAGE + "\n")
         return 2
     mips = mips or mip_filter is not None or alpha_weight
@@ -169,7 +214,18 @@ def main(argv=None):
             raise ValueError("-srgb: %s has no sRGB format code" % fmt)
         if mips and fmt in ("r11u", "r11s"):
             raise ValueError("-mips: %s has no image form, so no mip chain" % fmt)
-        image = load_rgba8(paths[0])
+        if (array or cube) and fmt in ("r11u", "r11s"):
+            raise ValueError("-%s: %s has no image form" % ("cube" if cube else "array", fmt))
+        if dds and (array or cube) and container.FORMATS[fmt][3] is None:
+            raise ValueError("%s has no DXGI format; use KTX" % fmt)
+        if cube and len(paths) > 2 and (len(paths) - 1) % 6 != 0:
+            raise ValueError("-cube takes the 6 faces of a cube (+X -X +Y -Y +Z -Z) or 6 n of a cube array, got %d inputs" % (len(paths) - 1))
+        if array or cube:
+            layers = load_layers(paths[:-1])
+            if cube and (layers.shape[0] % 6 != 0 or layers.shape[1] != layers.shape[2]):
+                raise ValueError("-cube needs 6 n square faces, got %d of %dx%d" % (layers.shape[0], layers.shape[2], layers.shape[1]))
+        else:
+            image = load_rgba8(paths[0])
     except (ValueError, OSError) as e:
         sys.stderr.write("%s\n" % e)
         return 1
@@ -182,6 +238,16 @@ def main(argv=None):
     if quality is not None:
         plan = api.BC7EncodingPlan()
         api.ConfigureBC7EncodingPlanFromQuality(plan, quality)
+    if array or cube:
+        h, w = layers.shape[1:3]
+        texture = encode_file_texture(layers, fmt, options, plan, mips=mips, mip_filter=mip_filter, order="layer" if dds else "level")
+        (container.write_dds_texture if dds else container.write_ktx_texture)(paths[-1], fmt, w, h, texture, cube, srgb)
+        for n, (image, levels) in enumerate(zip(layers, texture) if metrics else ()):
+            sys.stdout.write("layer %d\n" % n)
+            print_metrics(measure_file(image, fmt, levels[0], options))
+            if mips:
+                print_mip_metrics(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), w, h)
+        return 0
     h, w = image.shape[:2]
     if mips:
         levels = encode_file_mips(image, fmt, options, plan, mip_filter=mip_filter)
@@ -193,9 +259,7 @@ def main(argv=None):
     if metrics:
         print_metrics(measure_file(image, fmt, packed, options))
         if mips:
-            for l, report in enumerate(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), 1):
-                sys.stdout.write("mip %d %dx%d psnr %.4f dB (%s, %d texels)\n" % (l, max(1, w >> l), max(1, h >> l), report.psnr(),
-                                                                                  report.channels.upper(), report.texels))
+            print_mip_metrics(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), w, h)
     return 0
 
 

@@ -1,12 +1,14 @@
 """Compressed texture file -> decoded image on the MI355X: the reverse of packer.py, for the containers it writes.
 
-    python -m convectionkernels_amd.unpacker [-level L | -mips] input.ktx|input.dds output
+    python -m convectionkernels_amd.unpacker [-layer N] [-level L | -mips] input.ktx|input.dds output
 
 The container kind comes from the file's magic bytes (KTX 1.1, or DDS with the DX10 header), the format, the size and the mip
-levels from the file (container.read_ktx_mips / read_dds_mips).  The blocks are uploaded as the file holds them and decoded
+levels from the file (container.read_ktx_texture / read_dds_texture).  The blocks are uploaded as the file holds them and decoded
 straight into a linear image on the device (Context.decode_image: no padding to groups of eight, no untiling pass).
 output: a .npy of the decoded image, (H, W, 4) uint8 -- int8 for bc4s / bc5s, float16 for bc6hu / bc6hs; for the 8-bit
 unsigned formats any other extension is written by PIL as an RGBA image.
+-layer N: the layer of a texture array or cube file to decode (default 0; a cube's faces are layers 0..5 in the order +X -X +Y -Y
++Z -Z, cube n of a cube array starts at layer 6 n).  A layer is decoded like a file of its own, on views of the file's bytes.
 -level L: decode mip level L (default 0) alone.
 -mips: decode every level of the file (Context.decode_mips: one launch for the chain) and write each with its number put before
 the extension: out.0.npy, out.1.npy, ...
@@ -24,15 +26,23 @@ from . import container
 USAGE = __doc__.split("\n\n")[1]
 
 
-def read_levels(path):
-    """-> (format name, width, height, [blocks per level]) of a KTX or DDS file, told apart by the magic bytes"""
+def read_layers(path):
+    """-> (format name, width, height, layers[layer][level] blocks, cube) of a KTX or DDS file, told apart by the magic bytes"""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:12] == container._KTX_ID:
-        return container.read_ktx_mips(raw)
+        return container.read_ktx_texture(raw)
     if raw[:4] == container._DDS_MAGIC:
-        return container.read_dds_mips(raw)
+        return container.read_dds_texture(raw)
     raise ValueError("%s is neither a KTX 1.1 nor a DDS file" % path)
+
+
+def read_levels(path, layer=0):
+    """-> (format name, width, height, [blocks per level]) of one layer of a KTX or DDS file"""
+    fmt, width, height, layers, _ = read_layers(path)
+    if layer >= len(layers):
+        raise ValueError("%s has %d layer(s), no layer %d" % (path, len(layers), layer))
+    return fmt, width, height, layers[layer]
 
 
 def decode_file_levels(fmt, width, height, levels, ctx=None):
@@ -69,12 +79,15 @@ def write_image(path, image):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    level, mips, paths = None, False, []
+    level, mips, layer, paths = None, False, 0, []
     i = 0
     while i < len(argv):
         a = argv[i]
         if a == "-level" and i + 1 < len(argv) and argv[i + 1].isdigit():
             level = int(argv[i + 1])
+            i += 1
+        elif a == "-layer" and i + 1 < len(argv) and argv[i + 1].isdigit():
+            layer = int(argv[i + 1])
             i += 1
         elif a == "-mips":
             mips = True
@@ -88,7 +101,7 @@ def main(argv=None):
         sys.stderr.write(USAGE + "\n")
         return 2
     try:
-        fmt, width, height, levels = read_levels(paths[0])
+        fmt, width, height, levels = read_levels(paths[0], layer)
         if fmt in ("r11u", "r11s"):
             raise ValueError("%s: %s has no image form" % (paths[0], fmt))
         if (level or 0) >= len(levels):

@@ -370,8 +370,9 @@ int cvttmi_compact_rows_device(cvttmi_context *ctx, void *d_out, const void *d_p
  * multiple of 16 bytes, the level is made with 16-byte accesses.  CVTTMI_E_INVALID before anything is queued: NULL pointers,
  * levels 0 or too many, pyramidBytes below out[levels].byteOffset, an unknown pixel kind, rowPitchBytes below the row or no
  * multiple of the texel, a misaligned pointer.  Image and pyramid must not overlap.
- * There is no entry that encodes a chain: tile every level into its slot of the tile buffer (cvttmi_tile_image_device takes a
- * row pitch and any output offset), encode once, compact every level into its slot of the output. */
+ * A chain is encoded by cvttmi_encode_texture_device (below, with layers = 1), or by hand: tile every level into its slot of the
+ * tile buffer (cvttmi_tile_image_device takes a row pitch and any output offset), encode once, compact every level into its slot
+ * of the output. */
 #define CVTTMI_PIXELS_RGBA8_SNORM 2
 typedef struct cvttmi_mip_level
 {
@@ -393,6 +394,64 @@ int cvttmi_build_mips_filtered_device(cvttmi_context *ctx, void *d_pyramid, size
                                       uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, uint32_t filter,
                                       void *hipStream);
 int cvttmi_srgb_tables(uint16_t toLinear[256], uint32_t thresholds[255]);
+
+/* ---- texture arrays and cube maps (not part of the reference's API) ----
+ * A texture is `layers` images of one size, each with `levels` mip levels; layers = array elements x faces.  A cube is 6 layers
+ * in the order +X -X +Y -Y +Z -Z, a cube array 6 n layers.  Every layer has the chain of cvttmi_mip_layout; with T = that
+ * function's table for (width, height, pixelFormat, bytesPerBlock, levels) and E = T[levels].firstBlock, the packed output of
+ * the whole texture holds layers x E blocks in one of two orders:
+ *   CVTTMI_ORDER_LAYER_MAJOR  every layer's whole chain is consecutive (DDS):
+ *                             (layer, level) starts at block  layer * E + T[level].firstBlock
+ *   CVTTMI_ORDER_LEVEL_MAJOR  every level's layers are consecutive (KTX):
+ *                             (layer, level) starts at block  layers * T[level].firstBlock + layer * T[level].blockCount
+ * and holds T[level].blockCount blocks, row-major.  cvttmi_texture_subresource is the one owner of these two formulas.
+ * cvttmi_texture_layout: host only, no context; built on cvttmi_mip_layout's table.  pyramidLayerBytes = T[levels].byteOffset
+ *   rounded up to 256 (0 for one level), pyramidBytes = layers x that; tilesPerLayer = T[levels].firstTile, blocksPerLayer = E,
+ *   tiles / blocks = layers x those; workBytes = what cvttmi_encode_texture_device needs at d_work.  (The struct is named
+ *   cvttmi_texture_sizes: C has one name space for functions and typedefs.)
+ *   CVTTMI_E_INVALID, nothing written: NULL out, layers == 0, an unknown order, 2^32 or more tiles or blocks in total, any size
+ *   beyond size_t, and everything cvttmi_mip_layout rejects.
+ * cvttmi_texture_subresource: the same arguments and checks, and layer < layers, level < levels; either result pointer may be NULL.
+ * cvttmi_build_mips_array_device: cvttmi_build_mips_filtered_device for every layer.  Layer l's level 0 is at d_images +
+ *   l * layerPitchBytes (rowPitchBytes between rows), its levels 1 .. at d_pyramids + l * pyramidLayerBytes + T[L].byteOffset with
+ *   T[L].rowPitchBytes.  The same pixel kinds and filters by the same rules.  ONE launch per level for all layers (the layer is the
+ *   grid's z; arrays of more than 65535 layers take a launch per 65535 of them).  Writes exactly the levels' bytes: not the gaps that
+ *   align a level's start and not the space between layers.  A level is made with 16-byte accesses only where EVERY layer allows
+ *   them: the rule of cvttmi_build_mips_device with layerPitchBytes and pyramidLayerBytes under the same test; a layer pitch that is
+ *   no multiple of 16 sends level 1 of all layers through the texel-sized kernel.  CVTTMI_E_INVALID before anything is queued:
+ *   what the single-image call rejects, layers == 0, layerPitchBytes below height x rowPitchBytes or no multiple of the texel,
+ *   pyramidBytes below layers x pyramidLayerBytes.  levels == 1 launches nothing.
+ * cvttmi_encode_texture_device: images -> packed blocks in container order, everything on hipStream: the pyramids (levels > 1),
+ *   ONE tile launch for every level of every layer, one search over all tiles (groups of eight blocks are independent: the same
+ *   bytes as cvttmi_encode_device per level), ONE compact launch into d_out in `order`.  The pixel kind follows the format: RGBA16F
+ *   images for BC6HU / BC6HS, RGBA8 otherwise, averaged as int8 (CVTTMI_PIXELS_RGBA8_SNORM) for BC4S / BC5S; R11U / R11S have no
+ *   image form and are invalid.  options / plan / allocOptions: as for cvttmi_encode_device.  d_work: caller memory on a 256-byte
+ *   boundary, at least workBytes = cvttmi_texture_layout(.., that pixel kind, the format's bytes per block, ..).workBytes; it holds
+ *   pyramids, tiles and padded packed blocks, its layout is private and its contents after the call are unspecified.  The library
+ *   allocates and frees nothing in this call, and besides queueing the launches synchronises with nothing (BC7 orders itself after
+ *   the context's previous BC7 call as cvttmi_encode_device does).  Writes exactly outBytes = blocks x bytes per block at d_out
+ *   (any other outBytes is invalid) and nothing outside d_work[0, workBytes).  CVTTMI_E_INVALID before anything is queued, nothing
+ *   written: what the calls above reject, NULL pointers (plan: BC7 only), a misaligned pointer. */
+#define CVTTMI_ORDER_LAYER_MAJOR 0
+#define CVTTMI_ORDER_LEVEL_MAJOR 1
+typedef struct cvttmi_texture_sizes
+{
+    size_t pyramidLayerBytes, pyramidBytes;
+    size_t tilesPerLayer, tiles;
+    size_t blocksPerLayer, blocks;
+    size_t workBytes;
+} cvttmi_texture_sizes;
+int cvttmi_texture_layout(uint32_t width, uint32_t height, int pixelFormat, uint32_t bytesPerBlock, uint32_t levels, uint32_t layers,
+                          int order, cvttmi_texture_sizes *out);
+int cvttmi_texture_subresource(uint32_t width, uint32_t height, int pixelFormat, uint32_t bytesPerBlock, uint32_t levels, uint32_t layers,
+                               int order, uint32_t layer, uint32_t level, size_t *firstBlock, size_t *blockCount);
+int cvttmi_build_mips_array_device(cvttmi_context *ctx, void *d_pyramids, size_t pyramidBytes, const void *d_images, uint32_t width,
+                                   uint32_t height, size_t rowPitchBytes, size_t layerPitchBytes, int pixelFormat, uint32_t levels,
+                                   uint32_t layers, uint32_t filter, void *hipStream);
+int cvttmi_encode_texture_device(cvttmi_context *ctx, int format, void *d_out, size_t outBytes, const void *d_images, uint32_t width,
+                                 uint32_t height, size_t rowPitchBytes, size_t layerPitchBytes, uint32_t layers, uint32_t levels,
+                                 uint32_t filter, int order, const cvttmi_options *options, const cvttmi_bc7_plan *plan,
+                                 const cvttmi_options *allocOptions, void *d_work, size_t workBytes, void *hipStream);
 
 /* BC2 / BC3 / BC4 / BC5: cvtt::Kernels::EncodeBC2, EncodeBC3, EncodeBC4U/S, EncodeBC5U/S (reference
  * ConvectionKernels_API.cpp:101-199 -> S3TCComputer::PackRGB without alpha test, PackExplicitAlpha,
