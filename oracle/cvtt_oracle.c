@@ -519,6 +519,8 @@ typedef struct
     const float *rcp;
     int anyBlockHasAlpha; /* group-wide, BC67.cpp:1069 */
     int allowRGBModes;    /* group-wide, BC67.cpp:1072 */
+    uint32_t siteMask;    /* group-coupling site switch (cvtt_oracle.h): 0 = the reference's behaviour */
+    int siteLane;         /* the lane whose own flags answer a masked horizontal test */
 } bc7_ctx_t;
 
 /* Per-lane (= per block of the group) state of TrySinglePlane.
@@ -854,6 +856,9 @@ static void bc7_try_single_plane(const bc7_ctx_t *cx, bc7_lane_t *lanes)
                     allInvalid = allInvalid && lanes[l].punchThroughInvalid[pIter];
                     anyInvalid = anyInvalid || lanes[l].punchThroughInvalid[pIter];
                 }
+                /* site switch: AllSet / AnySet answered by the viewing lane's own flag */
+                if (cx->siteMask & ORC_SITE_BC7_PUNCH_COMMIT)
+                    allInvalid = anyInvalid = lanes[cx->siteLane].punchThroughInvalid[pIter];
                 if (allInvalid)
                     continue;
                 const int needPunchThroughCheck = anyInvalid;
@@ -874,6 +879,8 @@ static void bc7_try_single_plane(const bc7_ctx_t *cx, bc7_lane_t *lanes)
                             better[l] = lanes[l].shapeError < lanes[l].shapeBestError[shape];
                             anyBetter = anyBetter || better[l];
                         }
+                        if (cx->siteMask & ORC_SITE_BC7_PUNCH_COMMIT) /* site switch: own flag */
+                            anyBetter = better[cx->siteLane];
 
                         if (anyBetter)
                         {
@@ -887,6 +894,8 @@ static void bc7_try_single_plane(const bc7_ctx_t *cx, bc7_lane_t *lanes)
                                     better[l] = lanes[l].punchThroughInvalid[pIter] && !better[l];
                                     any = any || better[l];
                                 }
+                                if (cx->siteMask & ORC_SITE_BC7_PUNCH_COMMIT) /* site switch: own flag */
+                                    any = better[cx->siteLane];
                                 if (!any)
                                     punchThroughOK = 0;
                             }
@@ -1376,7 +1385,7 @@ static void bc7_emit(const bc7_work_t *work, uint8_t *out)
 
 /* BC7Computer::Pack for one group of 8 blocks, BC67.cpp:1975-2204 */
 static void bc7_encode_group(const uint8_t *blocks, uint8_t *out, const orc_options *options,
-                             const orc_bc7_plan *plan, const float *rcp)
+                             const orc_bc7_plan *plan, const float *rcp, uint32_t siteMask, int siteLane)
 {
     bc7_ctx_t cx;
     cx.flags = options->flags;
@@ -1386,10 +1395,13 @@ static void bc7_encode_group(const uint8_t *blocks, uint8_t *out, const orc_opti
     cx.plan = plan;
     cx.refineRounds = options->refineRoundsBC7;
     cx.rcp = rcp;
+    cx.siteMask = siteMask;
+    cx.siteLane = siteLane;
 
     /* group-wide booleans (AnySet over the 8 lanes), BC67.cpp:1066-1072 */
     cx.anyBlockHasAlpha = 0;
     cx.allowRGBModes = 0;
+    int ownAny = -1, ownRGB = -1;
     for (int b = 0; b < 8; b++)
     {
         int minAlpha = 255;
@@ -1400,7 +1412,12 @@ static void bc7_encode_group(const uint8_t *blocks, uint8_t *out, const orc_opti
         }
         if (minAlpha < 255) cx.anyBlockHasAlpha = 1;
         if (250 < minAlpha) cx.allowRGBModes = 1;
+        /* site switch: the viewing lane's own flag in place of the AnySet */
+        if (b == siteLane && (siteMask & ORC_SITE_BC7_ANY_ALPHA)) ownAny = minAlpha < 255;
+        if (b == siteLane && (siteMask & ORC_SITE_BC7_ALLOW_RGB)) ownRGB = 250 < minAlpha;
     }
+    if (ownAny >= 0) cx.anyBlockHasAlpha = ownAny;
+    if (ownRGB >= 0) cx.allowRGBModes = ownRGB;
 
     static __thread bc7_lane_t lanes[8];
     for (int b = 0; b < 8; b++)
@@ -1427,6 +1444,30 @@ static void bc7_encode_group(const uint8_t *blocks, uint8_t *out, const orc_opti
  * threading over groups
  * ---------------------------------------------------------------------------------- */
 /* `group` is the index of the group of 8 blocks: a job that also hands out per-block results indexes them with it */
+/* The site switch of cvtt_oracle.h for one group: with no bit of `relevant` set this is one plain encode.  Otherwise the
+ * group is encoded once per viewing lane and only that lane's block is kept, which is exactly "every masked horizontal
+ * test sees the block's own flag" and leaves every unmasked site group-wide. */
+#define ORC_RUN_SITED(siteMask, relevant, out, outStride, outBytes, CALL)          \
+    do                                                                             \
+    {                                                                              \
+        const uint32_t sitedMask = (siteMask) & (relevant);                        \
+        if (!sitedMask)                                                            \
+        {                                                                          \
+            uint8_t *sitedOut = (out);                                             \
+            const int siteLane = 0;                                                \
+            (void)siteLane;                                                        \
+            CALL;                                                                  \
+        }                                                                          \
+        else                                                                       \
+            for (int siteLane = 0; siteLane < 8; siteLane++)                       \
+            {                                                                      \
+                uint8_t sitedTmp[8 * 16];                                          \
+                uint8_t *sitedOut = sitedTmp;                                      \
+                CALL;                                                              \
+                memcpy((out) + siteLane * (outStride), sitedTmp + siteLane * (outStride), (outBytes)); \
+            }                                                                      \
+    } while (0)
+
 typedef void (*group_fn)(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group);
 
 typedef struct
@@ -1484,14 +1525,24 @@ static void run_groups(group_fn fn, const uint8_t *in, uint8_t *out, size_t numG
     free(tids);
 }
 
+typedef struct { const orc_options *options; uint32_t siteMask; } bc7_job_t;
+
 static void bc7_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)group;
-    bc7_encode_group(in, out, (const orc_options *)a, (const orc_bc7_plan *)b, rcp);
+    const bc7_job_t *job = (const bc7_job_t *)a;
+    ORC_RUN_SITED(job->siteMask, ORC_SITE_BC7_ANY_ALPHA | ORC_SITE_BC7_ALLOW_RGB | ORC_SITE_BC7_PUNCH_COMMIT, out, 16, 16,
+                  bc7_encode_group(in, sitedOut, job->options, (const orc_bc7_plan *)b, rcp, sitedMask, siteLane));
 }
 
 int orc_encode_bc7(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                    const orc_bc7_plan *plan, const float *rcp17, int threads)
+{
+    return orc_encode_bc7_sites(out, blocks, numBlocks, options, plan, rcp17, threads, 0);
+}
+
+int orc_encode_bc7_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                         const orc_bc7_plan *plan, const float *rcp17, int threads, uint32_t siteMask)
 {
     if (numBlocks % 8 != 0)
         return -1;
@@ -1501,7 +1552,8 @@ int orc_encode_bc7(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const 
         orc_probe_rcp(probed);
         rcp17 = probed;
     }
-    run_groups(bc7_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * 16, options, plan, rcp17, threads);
+    bc7_job_t job = {options, siteMask};
+    run_groups(bc7_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * 16, &job, plan, rcp17, threads);
     return 0;
 }
 
@@ -1519,7 +1571,7 @@ int orc_encode_bc7(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const 
 int orc_encode_bc1_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                        const float *rcp17, int threads, float *err)
 {
-    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, err);
+    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, err, 0);
 }
 
 int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, int format,
@@ -1531,5 +1583,5 @@ int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, c
 int orc_encode_etc2_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                         const orc_options *allocOptions, int mode, int threads, float *colorErr, uint32_t *alphaErr)
 {
-    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, colorErr, alphaErr);
+    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, colorErr, alphaErr, 0);
 }

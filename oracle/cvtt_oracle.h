@@ -104,6 +104,34 @@ int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, c
 int orc_encode_etc2_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                         const orc_options *allocOptions, int mode, int threads, float *colorErr, uint32_t *alphaErr);
 
+/* ---- group-coupling site switch (tests/test_group_coupling.py, tools/find_coupling_witnesses.py) ----
+ * Each bit makes ONE semantic AnySet / AllSet site of SURVEY App. B behave the way an encoder that got it wrong would:
+ * the horizontal test sees the block's own flag (or count) only, never its seven group mates'.  Block l of a group is
+ * then what a group encode gives for l when every masked horizontal test is answered with l's own value, so all the
+ * other coupling stays exactly as it is.  siteMask == 0 is the plain entry point, byte for byte. */
+enum
+{
+    ORC_SITE_BC7_ANY_ALPHA = 1 << 0,      /* anyBlockHasAlpha, BC67.cpp:1066-1069: own minAlpha < 255 */
+    ORC_SITE_BC7_ALLOW_RGB = 1 << 1,      /* allowRGBModes, BC67.cpp:1072: own minAlpha > 250 */
+    ORC_SITE_BC7_PUNCH_COMMIT = 1 << 2,   /* the AnySet / AllSet guards of the commit rule, BC67.cpp:1300-1303, 1406-1428: own flags */
+    ORC_SITE_BC6H_DUP_SKIP = 1 << 3,      /* AllSet(anySame), BC67.cpp:2868-2876: own anySame (the own round is dropped, refiner left empty) */
+    ORC_SITE_BC6H_COMMIT_LOOP = 1 << 4,   /* AnySet(errorBetter / needsCommit), BC67.cpp:2936-2984: own flags */
+    ORC_SITE_ETC2_OPAQUE_TMAX = 1 << 5,   /* opaque T mode: maxUniqueColors, ETC.cpp:563-584: own count (slot H2 never read) */
+    ORC_SITE_ETC2_PUNCH_TMAX = 1 << 6,    /* virtual T mode: clusterMaxLine and maxUniqueColors, ETC.cpp:1036-1142: own counts */
+    ORC_SITE_ETC2_PUNCH_ALPHA = 1 << 7,   /* AllSet(allTransparent) / AnySet(anyTransparent), ETC.cpp:1705-1867: own flags */
+    ORC_SITE_BC1_TEST_COUNTS = 1 << 8,    /* TestCounts' escape on the group's largest element count, S3TC.cpp:275-290: own count */
+    ORC_SITE_COUNT = 9
+};
+
+int orc_encode_bc7_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                         const orc_bc7_plan *plan, const float *rcp17, int threads, uint32_t siteMask);
+int orc_encode_bc1_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                         const float *rcp17, int threads, uint32_t siteMask);
+int orc_encode_bc6h_sites(uint8_t *out, const uint8_t *blocksF16, size_t numBlocks, const orc_options *options,
+                          int isSigned, const float *rcp17, int threads, uint32_t siteMask);
+int orc_encode_etc2_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                          const orc_options *allocOptions, int mode, int threads, uint32_t siteMask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,7 +395,7 @@ static void s3tc_test_counts(s3tc_lane_t *lanes, uint32_t flags, const int *coun
     }
 }
 
-static void s3tc_exhaustive_group(s3tc_lane_t *lanes, uint32_t flags, const float *rcp, int alphaTest)
+static void s3tc_exhaustive_group(s3tc_lane_t *lanes, uint32_t flags, const float *rcp, int alphaTest, uint32_t siteMask, int siteLane)
 {
     int groupMaxElements = 0;
     for (int l = 0; l < 8; l++)
@@ -435,6 +435,9 @@ static void s3tc_exhaustive_group(s3tc_lane_t *lanes, uint32_t flags, const floa
                 ln->pwSorted[15 - e][ch] = (float)ln->pixels[original][ch] * ln->w[ch];
         }
     }
+    /* site switch: TestCounts' escape tests the viewing lane's own element count, not the group's largest */
+    if (siteMask & ORC_SITE_BC1_TEST_COUNTS)
+        groupMaxElements = lanes[siteLane].numElements;
     for (int n0 = 0; n0 <= 15; n0++)
     {
         int remainingFor1 = 16 - n0;
@@ -478,13 +481,13 @@ static void s3tc_exhaustive_group(s3tc_lane_t *lanes, uint32_t flags, const floa
 /* PackRGB for a group of 8 blocks (outputs `stride` apart).  err: NULL, or 8 floats that receive each block's final
  * bestError, the score of the candidate that is emitted. */
 static void s3tc_pack_rgb_group(const uint8_t *blocks, uint8_t *out, size_t stride, const orc_options *options, const float *rcp, int alphaTest,
-                                float *err)
+                                float *err, uint32_t siteMask, int siteLane)
 {
     static __thread s3tc_lane_t lanes[8];
     for (int l = 0; l < 8; l++)
         s3tc_prepare(&lanes[l], blocks + l * 64, options, alphaTest);
     if (options->flags & ORC_FLAG_S3TC_EXHAUSTIVE)
-        s3tc_exhaustive_group(lanes, options->flags, rcp, alphaTest);
+        s3tc_exhaustive_group(lanes, options->flags, rcp, alphaTest, siteMask, siteLane);
     else
         for (int l = 0; l < 8; l++)
             s3tc_search(&lanes[l], options->flags, rcp, alphaTest);
@@ -503,17 +506,19 @@ static void s3tc_pack_rgb(const uint8_t *block, uint8_t *out, const orc_options 
     s3tc_emit(&ln, out);
 }
 
-typedef struct { const orc_options *options; float *err; /* NULL, or one float per block */ } bc1_job_t;
+typedef struct { const orc_options *options; float *err; /* NULL, or one float per block */ uint32_t siteMask; } bc1_job_t;
 
 static void bc1_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)b;
     const bc1_job_t *job = (const bc1_job_t *)a;
-    s3tc_pack_rgb_group(in, out, 8, job->options, rcp, 1, job->err ? job->err + group * 8 : NULL);
+    float *err = job->err ? job->err + group * 8 : NULL;
+    ORC_RUN_SITED(job->siteMask, ORC_SITE_BC1_TEST_COUNTS, out, 8, 8,
+                  s3tc_pack_rgb_group(in, sitedOut, 8, job->options, rcp, 1, sitedMask ? NULL : err, sitedMask, siteLane));
 }
 
 static int bc1_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
-                      const float *rcp17, int threads, float *err)
+                      const float *rcp17, int threads, float *err, uint32_t siteMask)
 {
     if (numBlocks % 8 != 0)
         return -1;
@@ -523,7 +528,7 @@ static int bc1_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, con
         orc_probe_rcp(probed);
         rcp17 = probed;
     }
-    bc1_job_t job = {options, err};
+    bc1_job_t job = {options, err, siteMask};
     run_groups(bc1_group_thunk, blocks, out, numBlocks / 8, 8 * 64, 8 * 8, &job, NULL, rcp17, threads);
     return 0;
 }
@@ -531,5 +536,11 @@ static int bc1_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, con
 int orc_encode_bc1(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                    const float *rcp17, int threads)
 {
-    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, NULL);
+    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, NULL, 0);
+}
+
+int orc_encode_bc1_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
+                         const float *rcp17, int threads, uint32_t siteMask)
+{
+    return bc1_encode(out, blocks, numBlocks, options, rcp17, threads, NULL, siteMask);
 }

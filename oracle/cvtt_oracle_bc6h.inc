@@ -435,7 +435,7 @@ static const uint8_t bc6h_modes_exist[2][17] = {
 
 /* BC6HComputer::Pack for one group, BC67.cpp:2665-3051 */
 static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const orc_options *options, int isSigned,
-                              const float *rcp)
+                              const float *rcp, uint32_t siteMask, int siteLane)
 {
     static __thread bc6h_lane_t lanes[8];
     const uint32_t flags = options->flags;
@@ -586,6 +586,10 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
                                 ln->anySame = anySame;
                                 allSame = allSame && anySame;
                             }
+                            /* site switch: AllSet(anySame) answered by the viewing lane's own anySame: its round is
+                             * dropped and its next refiner stays empty whenever IT repeats, whatever its mates do */
+                            if (siteMask & ORC_SITE_BC6H_DUP_SKIP)
+                                allSame = lanes[siteLane].anySame;
                             if (metaRound > 0 && allSame)
                             {
                                 roundValid[metaRound][subset] = 0;
@@ -704,6 +708,9 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
                             needsCommit[l] = errorBetter[l];
                             any = any || errorBetter[l];
                         }
+                        /* site switch: AnySet(errorBetter) / AnySet(needsCommit) answered by the viewing lane's own flags */
+                        if (siteMask & ORC_SITE_BC6H_COMMIT_LOOP)
+                            any = errorBetter[siteLane];
                         if (!any)
                             continue;
 #ifdef ORC_BC6H_STATS
@@ -729,7 +736,8 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
 #endif
                                 if (commit)
                                 {
-                                    anyCommit = 1;
+                                    if (!(siteMask & ORC_SITE_BC6H_COMMIT_LOOP) || l == siteLane)
+                                        anyCommit = 1;
                                     ln->bestError = combined[l];
                                     ln->bestMode = mode;
                                     ln->bestPartition = p;
@@ -747,6 +755,8 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
                             }
                             for (int l = 0; l < 8; l++)
                                 stillNeeds = stillNeeds || needsCommit[l];
+                            if (siteMask & ORC_SITE_BC6H_COMMIT_LOOP)
+                                stillNeeds = needsCommit[siteLane];
                             /* `continue` on no commit skips the needsCommit test (BC67.cpp:2954-2955) */
                             if (anyCommit && !stillNeeds)
                                 break;
@@ -771,18 +781,24 @@ static void bc6h_encode_group(const uint8_t *blocksBytes, uint8_t *out, const or
 static void bc6hu_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)group;
-    (void)b;
-    bc6h_encode_group(in, out, (const orc_options *)a, 0, rcp);
+    ORC_RUN_SITED(*(const uint32_t *)b, ORC_SITE_BC6H_DUP_SKIP | ORC_SITE_BC6H_COMMIT_LOOP, out, 16, 16,
+                  bc6h_encode_group(in, sitedOut, (const orc_options *)a, 0, rcp, sitedMask, siteLane));
 }
 static void bc6hs_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
     (void)group;
-    (void)b;
-    bc6h_encode_group(in, out, (const orc_options *)a, 1, rcp);
+    ORC_RUN_SITED(*(const uint32_t *)b, ORC_SITE_BC6H_DUP_SKIP | ORC_SITE_BC6H_COMMIT_LOOP, out, 16, 16,
+                  bc6h_encode_group(in, sitedOut, (const orc_options *)a, 1, rcp, sitedMask, siteLane));
 }
 
 int orc_encode_bc6h(uint8_t *out, const uint8_t *blocksF16, size_t numBlocks, const orc_options *options, int isSigned,
                     const float *rcp17, int threads)
+{
+    return orc_encode_bc6h_sites(out, blocksF16, numBlocks, options, isSigned, rcp17, threads, 0);
+}
+
+int orc_encode_bc6h_sites(uint8_t *out, const uint8_t *blocksF16, size_t numBlocks, const orc_options *options, int isSigned,
+                          const float *rcp17, int threads, uint32_t siteMask)
 {
     if (numBlocks % 8 != 0)
         return -1;
@@ -792,7 +808,7 @@ int orc_encode_bc6h(uint8_t *out, const uint8_t *blocksF16, size_t numBlocks, co
         orc_probe_rcp(probed);
         rcp17 = probed;
     }
-    run_groups(isSigned ? bc6hs_group_thunk : bc6hu_group_thunk, blocksF16, out, numBlocks / 8, 8 * 128, 8 * 16, options, NULL,
+    run_groups(isSigned ? bc6hs_group_thunk : bc6hu_group_thunk, blocksF16, out, numBlocks / 8, 8 * 128, 8 * 16, options, &siteMask,
                rcp17, threads);
     return 0;
 }

@@ -1615,7 +1615,8 @@ static void etc1_punchthrough(const etc_ctx_t *cx, etc_lane_t *ln)
 
 /* CompressETC2Block for one group, ETC.cpp:1664-1887 (cx->punchthrough selects EncodeETC2PunchthroughAlpha).
  * err: NULL, or 8 floats that receive each block's final bestError, the score of the candidate that is emitted. */
-static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t outStride, const etc_ctx_t *cx, float *err)
+static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t outStride, const etc_ctx_t *cx, float *err,
+                                    uint32_t siteMask, int siteLane)
 {
     static __thread etc_lane_t lanes[8];
     int groupAny = 0, groupAll = 1; /* AnySet(anyTransparent), AllSet(allTransparent) */
@@ -1636,6 +1637,12 @@ static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t 
             ln->allTransparent = 0;
         groupAny |= ln->anyTransparent;
         groupAll &= ln->allTransparent;
+    }
+    if (siteMask & ORC_SITE_ETC2_PUNCH_ALPHA)
+    {
+        /* site switch: AnySet / AllSet answered by the viewing lane's own flags */
+        groupAny = lanes[siteLane].anyTransparent;
+        groupAll = lanes[siteLane].allTransparent;
     }
     for (int l = 0; l < 8; l++)
     {
@@ -1681,6 +1688,8 @@ static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t 
             {
                 int colors[40];
                 int n = tmode_unique(cx, &ts, table, colors);
+                /* site switch: the viewing lane's own count in place of the group maximum (slot H2 is then never read) */
+                if ((siteMask & ORC_SITE_ETC2_OPAQUE_TMAX) && l != siteLane) continue;
                 if (n > gmax[table]) gmax[table] = n;
             }
         }
@@ -1711,11 +1720,15 @@ static void etc2_encode_group_color(const uint8_t *blocks, uint8_t *out, size_t 
                 vt_setup(cx, &lanes[l], flags[l], &vs[l]);
                 if (vs[l].numLine > clusterMaxLine) clusterMaxLine = vs[l].numLine;
             }
+            /* site switch: the viewing lane's own line count and unique-colour counts in place of the group maxima */
+            if (siteMask & ORC_SITE_ETC2_PUNCH_TMAX)
+                clusterMaxLine = vs[siteLane].numLine;
             for (int l = 0; l < 8; l++)
                 for (int table = 0; table < 8; table++)
                 {
                     int colors[40];
                     int n = vt_unique(cx, &vs[l], table, clusterMaxLine, colors);
+                    if ((siteMask & ORC_SITE_ETC2_PUNCH_TMAX) && l != siteLane) continue;
                     if (n > gmax[table]) gmax[table] = n;
                 }
             for (int l = 0; l < 8; l++)
@@ -1762,9 +1775,12 @@ typedef struct
 {
     etc_ctx_t cx;
     int mode;
+    uint32_t siteMask;  /* group-coupling site switch (cvtt_oracle.h) */
     float *colorErr;    /* NULL, or one float per block (modes 0, 1, 3, 4) */
     uint32_t *alphaErr; /* NULL, or one uint32 per block (modes 1, 2) */
 } etc_job_t;
+
+#define ETC2_SITES (ORC_SITE_ETC2_OPAQUE_TMAX | ORC_SITE_ETC2_PUNCH_TMAX | ORC_SITE_ETC2_PUNCH_ALPHA)
 
 static void etc2_group_thunk(const uint8_t *in, uint8_t *out, const void *a, const void *b, const float *rcp, size_t group)
 {
@@ -1774,13 +1790,15 @@ static void etc2_group_thunk(const uint8_t *in, uint8_t *out, const void *a, con
     float *cerr = job->colorErr ? job->colorErr + group * 8 : NULL;
     uint32_t *aerr = job->alphaErr ? job->alphaErr + group * 8 : NULL;
     if (job->mode == 0 || job->mode == 4)
-        etc2_encode_group_color(in, out, 8, &job->cx, cerr);
+        ORC_RUN_SITED(job->siteMask, ETC2_SITES, out, 8, 8,
+                      etc2_encode_group_color(in, sitedOut, 8, &job->cx, sitedMask ? NULL : cerr, sitedMask, siteLane));
     else if (job->mode == 3)
         etc1_encode_group(in, out, &job->cx, cerr);
     else if (job->mode == 1)
     {
         /* EncodeETC2RGBA, API.cpp:270-286: [alpha 8 B | colour 8 B] */
-        etc2_encode_group_color(in, out + 8, 16, &job->cx, cerr);
+        ORC_RUN_SITED(job->siteMask, ETC2_SITES, out + 8, 16, 8,
+                      etc2_encode_group_color(in, sitedOut, 16, &job->cx, sitedMask ? NULL : cerr, sitedMask, siteLane));
         for (int l = 0; l < 8; l++)
             etc2_alpha_block(in + l * 64, out + l * 16, aerr ? aerr + l : NULL);
     }
@@ -1797,12 +1815,13 @@ int orc_encode_etc2(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const
 /* allocOptions: the Options AllocETC2Data was called with; the two chroma axes are computed from ITS colour weights when the
  * scratch is constructed (ETC.cpp:3117-3145), everything else comes from the Options of the Encode call */
 static int etc2_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
-                       int mode, int threads, float *colorErr, uint32_t *alphaErr)
+                       int mode, int threads, float *colorErr, uint32_t *alphaErr, uint32_t siteMask)
 {
     if (numBlocks % 8 != 0 || mode < 0 || mode > 4) /* 3 = ETC1 (EncodeETC1, API.cpp:201-214), 4 = EncodeETC2PunchthroughAlpha (231-244) */
         return -1;
     etc_job_t job;
     job.mode = mode;
+    job.siteMask = siteMask;
     job.colorErr = mode == 2 ? NULL : colorErr;
     job.alphaErr = (mode == 1 || mode == 2) ? alphaErr : NULL;
     job.cx.flags = options->flags;
@@ -1828,5 +1847,11 @@ static int etc2_encode(uint8_t *out, const uint8_t *blocks, size_t numBlocks, co
 int orc_encode_etc2_alloc(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
                           int mode, int threads)
 {
-    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, NULL, NULL);
+    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, NULL, NULL, 0);
+}
+
+int orc_encode_etc2_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options, const orc_options *allocOptions,
+                          int mode, int threads, uint32_t siteMask)
+{
+    return etc2_encode(out, blocks, numBlocks, options, allocOptions, mode, threads, NULL, NULL, siteMask);
 }

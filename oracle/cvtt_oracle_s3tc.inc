@@ -262,7 +262,7 @@ static void s3tc_group_thunk(const uint8_t *in, uint8_t *out, const void *a, con
     const s3tc_job_t *job = (const s3tc_job_t *)a;
     const orc_options *o = job->options;
     if (job->format == 2 || job->format == 3)
-        s3tc_pack_rgb_group(in, out + 8, 16, o, rcp, 0, job->colorErr ? job->colorErr + group * 8 : NULL);
+        s3tc_pack_rgb_group(in, out + 8, 16, o, rcp, 0, job->colorErr ? job->colorErr + group * 8 : NULL, 0, 0);
     const int alphaChannels = job->format >= 6 ? 2 : 1;
     for (int blk = 0; blk < 8; blk++)
     {

@@ -28,6 +28,20 @@ FLAG_UNIFORM = 0x200
 FLAGS_DEFAULT = FLAG_BC7_FAST_INDEXING | FLAG_S3TC_PARANOID
 FLAGS_BETTER = FLAG_S3TC_PARANOID | FLAG_S3TC_EXHAUSTIVE
 
+# group-coupling site switch of the restatement (cvtt_oracle.h): one bit per semantic AnySet / AllSet site of SURVEY
+# App. B; a set bit makes that site see the block's own flag only.  Name -> (bit, encoder family).
+SITES = {
+    "bc7_any_alpha": (1 << 0, "bc7"),
+    "bc7_allow_rgb": (1 << 1, "bc7"),
+    "bc7_punch_commit": (1 << 2, "bc7"),
+    "bc6h_dup_skip": (1 << 3, "bc6h"),
+    "bc6h_commit_loop": (1 << 4, "bc6h"),
+    "etc2_opaque_tmax": (1 << 5, "etc2"),
+    "etc2_punch_tmax": (1 << 6, "etc2"),
+    "etc2_punch_alpha": (1 << 7, "etc2"),
+    "bc1_test_counts": (1 << 8, "bc1"),
+}
+
 
 def _u8(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
@@ -214,13 +228,16 @@ class OracleLib:
         L.orc_encode_bc1.restype = ctypes.c_int
         L.orc_encode_bc6h.restype = ctypes.c_int
         L.orc_encode_etc2.restype = ctypes.c_int
+        for n in ("orc_encode_bc7_sites", "orc_encode_bc1_sites", "orc_encode_bc6h_sites", "orc_encode_etc2_sites"):
+            getattr(L, n).restype = ctypes.c_int
 
     def probe_rcp(self):
         out = np.zeros(17, np.float32)
         self.lib.orc_probe_rcp(out.ctypes.data_as(ctypes.c_void_p))
         return out
 
-    def encode_bc7(self, blocks, options, plan, rcp=None, threads=1):
+    def encode_bc7(self, blocks, options, plan, rcp=None, threads=1, site_mask=0):
+        """site_mask: group-coupling site switch (SITES); 0 = the reference's behaviour."""
         blocks, pb = _u8(blocks)
         n = blocks.size // 64
         assert n % 8 == 0
@@ -230,14 +247,14 @@ class OracleLib:
             rcp = np.ascontiguousarray(rcp, np.float32)
             assert rcp.size == 17
             rcp_p = rcp.ctypes.data_as(ctypes.c_void_p)
-        rc = self.lib.orc_encode_bc7(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
-                                     options.ctypes.data_as(ctypes.c_void_p), plan.ctypes.data_as(ctypes.c_void_p),
-                                     rcp_p, ctypes.c_int(threads))
+        rc = self.lib.orc_encode_bc7_sites(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                           options.ctypes.data_as(ctypes.c_void_p), plan.ctypes.data_as(ctypes.c_void_p),
+                                           rcp_p, ctypes.c_int(threads), ctypes.c_uint32(site_mask))
         if rc != 0:
             raise RuntimeError("orc_encode_bc7 rc=%d" % rc)
         return out.reshape(n, 16)
 
-    def encode_bc6h(self, blocks_f16bits, options, signed=False, rcp=None, threads=1):
+    def encode_bc6h(self, blocks_f16bits, options, signed=False, rcp=None, threads=1, site_mask=0):
         b = np.ascontiguousarray(blocks_f16bits, dtype=np.int16)
         n = b.size // 64
         assert n % 8 == 0
@@ -246,13 +263,14 @@ class OracleLib:
         if rcp is not None:
             rcp = np.ascontiguousarray(rcp, np.float32)
             rcp_p = rcp.ctypes.data_as(ctypes.c_void_p)
-        rc = self.lib.orc_encode_bc6h(out.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n),
-                                      options.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(int(signed)), rcp_p, ctypes.c_int(threads))
+        rc = self.lib.orc_encode_bc6h_sites(out.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n),
+                                            options.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(int(signed)), rcp_p, ctypes.c_int(threads),
+                                            ctypes.c_uint32(site_mask))
         if rc != 0:
             raise RuntimeError("orc_encode_bc6h rc=%d" % rc)
         return out.reshape(n, 16)
 
-    def encode_etc2(self, blocks, options, mode, threads=1, alloc_options=None):
+    def encode_etc2(self, blocks, options, mode, threads=1, alloc_options=None, site_mask=0):
         """mode 0: ETC2 RGB (8 B), 1: ETC2 RGBA (16 B), 2: EAC alpha (8 B), 3: ETC1 (8 B), 4: ETC2 punch-through alpha (8 B).
         alloc_options: the Options handed to AllocETC2Data (default: the encode options)."""
         blocks, pb = _u8(blocks)
@@ -261,9 +279,10 @@ class OracleLib:
         per = 16 if mode == 1 else 8
         out = np.zeros(n * per, np.uint8)
         ao = options if alloc_options is None else alloc_options
-        self.lib.orc_encode_etc2_alloc.restype = ctypes.c_int
-        rc = self.lib.orc_encode_etc2_alloc(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
-                                            options.ctypes.data_as(ctypes.c_void_p), ao.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(mode), ctypes.c_int(threads))
+        self.lib.orc_encode_etc2_sites.restype = ctypes.c_int
+        rc = self.lib.orc_encode_etc2_sites(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                            options.ctypes.data_as(ctypes.c_void_p), ao.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(mode), ctypes.c_int(threads),
+                                            ctypes.c_uint32(site_mask))
         if rc != 0:
             raise RuntimeError("orc_encode_etc2 rc=%d" % rc)
         return out.reshape(n, per)
@@ -361,7 +380,7 @@ class OracleLib:
             raise RuntimeError("orc_encode_eac11 rc=%d" % rc)
         return out.reshape(n, 8)
 
-    def encode_bc1(self, blocks, options, rcp=None, threads=1):
+    def encode_bc1(self, blocks, options, rcp=None, threads=1, site_mask=0):
         blocks, pb = _u8(blocks)
         n = blocks.size // 64
         assert n % 8 == 0
@@ -370,8 +389,8 @@ class OracleLib:
         if rcp is not None:
             rcp = np.ascontiguousarray(rcp, np.float32)
             rcp_p = rcp.ctypes.data_as(ctypes.c_void_p)
-        rc = self.lib.orc_encode_bc1(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
-                                     options.ctypes.data_as(ctypes.c_void_p), rcp_p, ctypes.c_int(threads))
+        rc = self.lib.orc_encode_bc1_sites(out.ctypes.data_as(ctypes.c_void_p), pb, ctypes.c_size_t(n),
+                                           options.ctypes.data_as(ctypes.c_void_p), rcp_p, ctypes.c_int(threads), ctypes.c_uint32(site_mask))
         if rc != 0:
             raise RuntimeError("orc_encode_bc1 rc=%d" % rc)
         return out.reshape(n, 8)

@@ -11,6 +11,9 @@ Outputs (data only -- inputs, expected outputs, the generating host's RCPPS tabl
                                     `--only-mode-census` writes this file alone
     tests/golden/bc7_single_candidate.npz  every single-candidate BC7 plan of tests/bc7_bound_ref.py on 64 blocks;
                                     `--only-bc7-single-candidate` writes this file alone
+    tests/golden/group_coupling.npz witness groups of every group-of-8 coupling site, searched for on the C restatement by
+                                    tools/find_coupling_witnesses.py, with the reference's bytes next to the restatement's;
+                                    `--only-group-coupling` writes this file alone
 """
 import hashlib
 import json
@@ -113,6 +116,13 @@ def bc7_single_candidate(ref, fast, rcp):
                         candidates=np.array(cands, np.int32), packed=packed)
 
 
+def group_coupling():
+    """tests/golden/group_coupling.npz: the seeded witness search of tools/find_coupling_witnesses.py (a few CPU-minutes)"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import find_coupling_witnesses
+    find_coupling_witnesses.build()
+
+
 def main():
     ref = pyref.RefLib()
     fast = pyref.RefLib(fast=True)
@@ -121,10 +131,14 @@ def main():
     if "--only-bc7-single-candidate" in sys.argv:
         bc7_single_candidate(ref, fast, rcp)
         return
+    if "--only-group-coupling" in sys.argv:
+        group_coupling()
+        return
     mode_census(ref, fast, rcp)
     if "--only-mode-census" in sys.argv:
         return
     bc7_single_candidate(ref, fast, rcp)
+    group_coupling()
 
     # ---- mixed content x variants ----
     blocks = content.mixed_ldr_blocks(20260929, 24)

@@ -44,6 +44,22 @@ def test_group_coupling_changes_output(oracle_lib):
     opt = pyref.make_options()
     grouped = oracle_lib.encode_bc6h(blocks, opt, False, None, 8)
     assert grouped.shape == (128, 16)
+    # the witness groups of tests/golden/group_coupling.npz (blocks whose bytes change when one of the two sites sees the
+    # block's own flag only).  A block replicated into all eight slots is a block for which BOTH sites see nothing but its own
+    # flags: it must encode exactly as the restatement's site switch says with both bits set (the two sites interact, so a
+    # witness of one site alone can come out as in its group again: 3 of 39 blocks of bc6h_dup_skip_u do), and on every block
+    # that switch changes, alone differs from grouped
+    g = np.load(os.path.join(GOLD, "group_coupling.npz"))
+    both = pyref.SITES["bc6h_dup_skip"][0] | pyref.SITES["bc6h_commit_loop"][0]
+    for name, signed in (("bc6h_dup_skip_u", False), ("bc6h_commit_loop_u", False), ("bc6h_dup_skip_s", True), ("bc6h_commit_loop_s", True)):
+        src, o = g["src_" + name], g["opt_" + name]
+        assert np.count_nonzero(g["wit_" + name]) >= 8, name
+        grouped = oracle_lib.encode_bc6h(src, o, signed, g["rcp"], 8)
+        assert (grouped == g["out_" + name]).all(), name
+        alone = oracle_lib.encode_bc6h(np.repeat(src, 8, axis=0), o, signed, g["rcp"], 8)[::8]
+        assert (alone == oracle_lib.encode_bc6h(src, o, signed, g["rcp"], 8, site_mask=both)).all(), name
+        differ = (alone != grouped).any(axis=1)
+        assert np.count_nonzero(differ & (g["wit_" + name] > 0)) >= 8, (name, np.count_nonzero(differ))
 
 
 # ------------------------------------------------------------------ GPU

@@ -116,6 +116,19 @@ def test_t_mode_group_coupling(oracle_lib):
     blocks = content.mixed_ldr_blocks(8, 12)
     out = oracle_lib.encode_etc2(blocks, pyref.make_options(), 0, 4)
     assert out.shape == (96, 8)
+    # the witnesses of tests/golden/group_coupling.npz: blocks that take the zero slot past their own unique line colours,
+    # which exists only while a mate has more of them.  Replicated into all eight slots no block has more, and ETC1 has no T mode
+    g = np.load(os.path.join(GOLD, "group_coupling.npz"))
+    src, wit = g["src_etc2_opaque_tmax"], np.flatnonzero(g["wit_etc2_opaque_tmax"])
+    assert wit.size >= 8
+    opt = g["opt_etc2_opaque_tmax"]
+    grouped = oracle_lib.encode_etc2(src, opt, 0, 4)
+    assert (grouped == g["out_etc2_opaque_tmax"]).all()
+    rep = np.repeat(src[wit], 8, axis=0)
+    alone = oracle_lib.encode_etc2(rep, opt, 0, 4)[::8]
+    same = wit[(alone == grouped[wit]).all(axis=1)]
+    assert same.size == 0, "witnesses %s encode alone as they do in their group" % same
+    assert (oracle_lib.encode_etc2(rep, opt, 3, 4)[::8] == oracle_lib.encode_etc2(src, opt, 3, 4)[wit]).all()
 
 
 # ------------------------------------------------------------------ GPU

@@ -87,8 +87,18 @@ def test_group_coupling_is_modelled(oracle_lib):
     for i in range(64):
         rep = np.repeat(blocks[i:i + 1], 8, axis=0)
         alone[i] = oracle_lib.encode_bc7(rep, opt, plan)[0]
-    # not asserting inequality (coupling rarely flips a bit); both must be valid encodings
     assert grouped.shape == alone.shape
+    # on random content the coupling rarely flips a bit; on the witnesses of tests/golden/group_coupling.npz (blocks whose
+    # bytes change when allowRGBModes / anyBlockHasAlpha see the block's own alpha only) it must
+    g = np.load(os.path.join(GOLD, "group_coupling.npz"))
+    for name in ("bc7_allow_rgb", "bc7_any_alpha"):
+        src, wit = g["src_" + name], np.flatnonzero(g["wit_" + name])
+        assert wit.size >= 8, name
+        grouped = oracle_lib.encode_bc7(src, g["opt_" + name], g["plan_" + name], g["rcp"], threads=8)
+        assert (grouped == g["out_" + name]).all(), name
+        alone = oracle_lib.encode_bc7(np.repeat(src[wit], 8, axis=0), g["opt_" + name], g["plan_" + name], g["rcp"], threads=8)[::8]
+        same = wit[(alone == grouped[wit]).all(axis=1)]
+        assert same.size == 0, "%s: witnesses %s encode alone as they do in their group" % (name, same)
 
 
 def test_against_reference_fresh_inputs(oracle_lib, ref_lib):
