@@ -201,7 +201,7 @@ _EXPORTS = (
     "cvttmi_format_info", "cvttmi_encode_device", "cvttmi_encode",
     "cvttmi_mip_level_count", "cvttmi_mip_layout", "cvttmi_build_mips_device",
     "cvttmi_decode_image_device", "cvttmi_decode_mips_device",
-    "cvttmi_build_mips_filtered_device", "cvttmi_srgb_tables",
+    "cvttmi_build_mips_filtered_device", "cvttmi_srgb_tables", "cvttmi_mip_kernel_taps",
     "cvttmi_texture_layout", "cvttmi_texture_subresource", "cvttmi_build_mips_array_device", "cvttmi_encode_texture_device",
 )
 
@@ -296,6 +296,7 @@ def load_library():
                                                       ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.c_void_p]
     lib.cvttmi_srgb_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.cvttmi_mip_kernel_taps.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
     U = ctypes.c_uint32
     lib.cvttmi_texture_layout.argtypes = [U, U, I, U, U, U, I, P]
     lib.cvttmi_texture_subresource.argtypes = [U, U, I, U, U, U, I, U, U, ctypes.POINTER(N), ctypes.POINTER(N)]
@@ -387,6 +388,33 @@ def mip_filter_value(filter):
     if isinstance(filter, bool) or not isinstance(filter, int) or not 0 <= filter <= 0xFFFFFFFF:
         raise CvttError("mip filter must be a name or a MIP_FILTER_* value, got %r" % (filter,))
     return filter
+
+
+# mip kernels and wrap modes (include/cvtt_mi355x.h CVTTMI_MIP_KERNEL_*, CVTTMI_MIP_WRAP_*): two more fields of the filter word
+MIP_KERNELS = {"triangle": 0x10, "mitchell": 0x20, "lanczos3": 0x30, "kaiser": 0x40}
+MIP_WRAPS = {"clamp": 0, "repeat": 0x200, "mirror": 0x400}
+
+
+def mip_filter_word(filter, kernel=None, wrap="clamp"):
+    """the `filter` value of the C calls: mip_filter_value(filter) with the kernel (a name of MIP_KERNELS or None = the 2x2 rule)
+    and the wrap mode (a name of MIP_WRAPS) OR-ed on"""
+    if kernel is not None and kernel not in MIP_KERNELS:
+        raise CvttError("unknown mip kernel %r (one of %s)" % (kernel, ", ".join(MIP_KERNELS)))
+    if wrap not in MIP_WRAPS:
+        raise CvttError("unknown wrap mode %r (one of %s)" % (wrap, ", ".join(MIP_WRAPS)))
+    return mip_filter_value(filter) | (MIP_KERNELS[kernel] if kernel is not None else 0) | MIP_WRAPS[wrap]
+
+
+def mip_kernel_taps(name):
+    """cvttmi_mip_kernel_taps: the Q14 tap table of a mip kernel (a name of MIP_KERNELS), int16, 4 R entries summing to 16384"""
+    import numpy as np
+    if name not in MIP_KERNELS:
+        raise CvttError("unknown mip kernel %r (one of %s)" % (name, ", ".join(MIP_KERNELS)))
+    taps, count = np.zeros(12, np.int16), ctypes.c_uint32(0)
+    rc = load_library().cvttmi_mip_kernel_taps(MIP_KERNELS[name], taps.ctypes.data, ctypes.byref(count))
+    if rc != 0:
+        raise CvttError("cvttmi_mip_kernel_taps failed (%d)" % rc)
+    return taps[:count.value].copy()
 
 
 def srgb_tables():
@@ -1006,7 +1034,7 @@ class Context:
         return image if image.stride(2) == 1 and image.stride(1) == 4 else image.contiguous()
 
     # -- mip chains: 2x2 filter on the device, and the whole chain through one encode call --
-    def build_mips(self, image, levels=None, signed=False, stream=None, filter="box"):
+    def build_mips(self, image, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
         """(H,W,4) CUDA image -> the list of its mip levels (cvttmi_build_mips_device): [0] is the image itself, the others are
         (h_L, w_L, 4) views of the image's dtype into ONE allocation laid out by mip_layout.  Level L+1 is max(1, w_L >> 1) x
         max(1, h_L >> 1), a 2x2 box of the rounded level L (an odd last row / column is dropped).  uint8: (a+b+c+d+2) >> 2;
@@ -1014,7 +1042,11 @@ class Context:
         ((a+b)+(c+d)) * 0.25 in float, rounded to nearest even.  levels: None = the full chain down to 1x1.
         filter (cvttmi_build_mips_filtered_device; a name or a MIP_FILTER_* value): "box" is the rule above; "srgb" averages the
         colour channels of a uint8 image in linear light; "box+alpha" / "srgb+alpha" weight them by the texels' alphas; "normal"
-        renormalises the summed vectors of a uint8 or int8 normal map.  Alpha always takes the box rule."""
+        renormalises the summed vectors of a uint8 or int8 normal map.  Alpha always takes the box rule.
+        kernel: None = the 2x2 rules above; "triangle", "mitchell", "lanczos3" or "kaiser" (MIP_KERNELS) filters every level with
+        that kernel's 4 / 8 / 12 taps per direction instead, under "box" (the plain rule), "srgb" or "normal", uint8 or int8
+        images; an odd last row / column is then read as a neighbour.  wrap: how the taps leave the image: "clamp", "repeat" (a
+        tiling texture) or "mirror"; only with a kernel."""
         import torch
         image = self._image_in(image)
         h, w = int(image.shape[0]), int(image.shape[1])
@@ -1026,23 +1058,24 @@ class Context:
         pyramid = torch.empty(layout.pyramid_bytes, dtype=torch.uint8, device=image.device)
         stream = self._stream(stream, image.device)
         self._check(self._lib.cvttmi_build_mips_filtered_device(self._h, pyramid.data_ptr(), layout.pyramid_bytes, image.data_ptr(), w, h,
-                                                                image.stride(0) * esz, kind, len(layout), mip_filter_value(filter),
+                                                                image.stride(0) * esz, kind, len(layout), mip_filter_word(filter, kernel, wrap),
                                                                 ctypes.c_void_p(stream)), "build_mips")
         return [image] + [pyramid[L.byteOffset: L.byteOffset + L.rowPitchBytes * L.height].view(image.dtype).view(L.height, L.width, 4)
                           for L in layout[1:]]
 
-    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box"):
+    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box", kernel=None, wrap="clamp"):
         """(H,W,4) CUDA image -> the packed blocks of every mip level: a list of (ceil(w_L/4) * ceil(h_L/4), bytes per block)
         uint8 views, level 0 first, consecutive in one allocation (container order).  Level L equals
         encode_image(fmt, build_mips(image)[L]) byte for byte; the levels are tiled into one block tensor and searched by ONE
         encode call (groups of eight blocks are independent), so the small levels cost no launches of their own.  fmt as for
         encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain.  mip_filter: build_mips's
-        `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L])."""
+        `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L]); kernel, wrap:
+        build_mips's, and the same holds under them."""
         import torch
         if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
         _, bpb, _, _ = TEXTURE_FORMATS[fmt]
-        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream, filter=mip_filter)
+        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream, filter=mip_filter, kernel=kernel, wrap=wrap)
         image = images[0]
         esz = image.element_size()
         layout = mip_layout(int(image.shape[1]), int(image.shape[0]), 4 * esz, bpb, len(images))
@@ -1085,11 +1118,11 @@ class Context:
         esz = images.element_size()
         return images, row * esz, layer * esz
 
-    def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box"):
+    def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
         """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): build_mips
         for every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
         into one allocation: layer l's chain as mip_layout places it, texture_layout's pyramidLayerBytes apart.  levels, signed,
-        filter: as for build_mips."""
+        filter, kernel, wrap: as for build_mips."""
         import torch
         images, row_pitch, layer_pitch = self._images_in(images)
         n, h, w = (int(v) for v in images.shape[:3])
@@ -1101,7 +1134,7 @@ class Context:
         sizes = texture_layout(w, h, 4 * esz, 16, len(layout), n)
         pyramids = torch.empty(sizes.pyramidBytes, dtype=torch.uint8, device=images.device)
         self._check(self._lib.cvttmi_build_mips_array_device(self._h, pyramids.data_ptr(), sizes.pyramidBytes, images.data_ptr(), w, h, row_pitch,
-                                                             layer_pitch, kind, len(layout), n, mip_filter_value(filter),
+                                                             layer_pitch, kind, len(layout), n, mip_filter_word(filter, kernel, wrap),
                                                              ctypes.c_void_p(self._stream(stream, images.device))), "build_mips_array")
         # one strided view per level over all layers, then its n slices (pyramidLayerBytes is a multiple of 256: whole elements)
         typed = pyramids.view(images.dtype)
@@ -1109,12 +1142,13 @@ class Context:
                                                            L.byteOffset // esz).unbind(0) for L in layout[1:]]
         return [[views[l] for views in per_level] for l in range(n)]
 
-    def encode_texture(self, fmt, images, options=None, plan=None, levels=None, order="layer", mip_filter="box", stream=None):
+    def encode_texture(self, fmt, images, options=None, plan=None, levels=None, order="layer", mip_filter="box", stream=None, kernel=None,
+                       wrap="clamp"):
         """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones): the layers of a texture array, or the 6 n faces of a cube (array)
         in the order +X -X +Y -Y +Z -Z -> TextureBlocks: [layer][level] packed blocks, uint8 views into ONE allocation (.base) in
         `order`: "layer" = every layer's chain consecutive (DDS), "level" = every level's layers consecutive (KTX).  One C call
         (cvttmi_encode_texture_device): the mips of all layers a launch per level, one tile launch, one search, one compact launch.
-        [l][L] equals encode_mips(fmt, images[l], ..)[L] byte for byte.  fmt, levels, mip_filter: as for encode_mips."""
+        [l][L] equals encode_mips(fmt, images[l], ..)[L] byte for byte.  fmt, levels, mip_filter, kernel, wrap: as for encode_mips."""
         import torch
         if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
@@ -1133,7 +1167,8 @@ class Context:
         out = torch.empty((sizes.blocks, bpb), dtype=torch.uint8, device=images.device)
         work = torch.empty(sizes.workBytes, dtype=torch.uint8, device=images.device)
         self._check(self._lib.cvttmi_encode_texture_device(self._h, fid, out.data_ptr(), sizes.blocks * bpb, images.data_ptr(), w, h, row_pitch,
-                                                           layer_pitch, n, levels, mip_filter_value(mip_filter), ov, ctypes.addressof(options),
+                                                           layer_pitch, n, levels, mip_filter_word(mip_filter, kernel, wrap), ov,
+                                                           ctypes.addressof(options),
                                                            ctypes.addressof(plan) if plan is not None else None, None, work.data_ptr(),
                                                            sizes.workBytes, ctypes.c_void_p(self._stream(stream, images.device))),
                     "encode_texture(%s)" % fmt)

@@ -1,0 +1,378 @@
+// The mip kernels wider than 2x2 (include/cvtt_mi355x.h, "mip chains", CVTTMI_MIP_KERNEL_* and CVTTMI_MIP_WRAP_*): one level per
+// launch like the other mip filters, RGBA8 and RGBA8_SNORM texels only.  An output texel reads n x n source texels (n = 4, 8 or
+// 12 taps per direction, one Q14 table for every texel: tools/gen_mip_kernels.py), separably:
+//   a workgroup of 256 lanes owns a tile of kTileX x kTileY output texels.  Horizontal pass: for each of the 2 kTileY + n - 2
+//   source rows under the tile (wrapped), a lane makes four neighbouring h' from one window of n + 6 source texels -- 16-byte
+//   reads where the chunk lies inside the row and the row starts allow them, texel reads through the wrap otherwise -- and stores
+//   them in LDS.  Vertical pass: a lane makes four output texels of one column from a window of n + 6 LDS entries and writes
+//   each with a 4-byte store (a wave writes 256 contiguous bytes of a row).
+// The value of a texel's channel is taken in the horizontal pass: the byte (plain, and always channel 3), T[byte] (SRGB) or X
+// (NORMAL).  LDS per entry: plain int16 x 4; SRGB int32 x 4; NORMAL int16 x 4 of X and alpha plus int16 x 4 of the plain
+// bytes, which the vertical pass reads only where the three sums of X are all zero.  At most 42 x 64 x 16 B + the sRGB tables =
+// 48.5 KB a workgroup: three workgroups share a CU.  The taps arrive as kernel arguments (scalar registers).  No scratch.
+// Every product is a 24-bit multiply (__mul24: full rate, where a 32-bit multiply runs at a quarter): a tap is below 2^13, a value
+// or an h' below 2^17 (sRGB: T <= 65535, |h'| <= 78727), and the generator asserts that the sums stay inside int32.
+#include "mip_common.h"
+#include <type_traits>
+
+#define CVTT_SRGB_TABLE __device__ const __attribute__((aligned(16))) // (the byte table is copied a word at a time)
+#include "srgb_tables.h"
+
+namespace
+{
+enum
+{
+    kPlain = 0,
+    kSrgb = 1,
+    kNormal = 2,
+    kWrapRepeat = 0x200,
+    kWrapMirror = 0x400,
+    kTileX = 64,
+    kTileY = 16
+};
+
+struct MipTaps
+{
+    int w[12];
+};
+
+struct SrgbTables
+{
+    uint32_t next[256]; // [c] = U[c + 1], the threshold above code c; [255] = no sum reaches it
+    uint16_t lin[256];
+    uint8_t coarse[4096];
+};
+
+__device__ __forceinline__ void loadSrgbTables(SrgbTables &t)
+{
+    for (uint32_t i = threadIdx.x; i < 256u; i += 256u)
+    {
+        t.next[i] = i < 255u ? k_srgbThresholds[i] : 0xffffffffu;
+        t.lin[i] = k_srgbToLinear[i];
+    }
+    for (uint32_t i = threadIdx.x; i < 1024u; i += 256u)
+        reinterpret_cast<uint32_t *>(t.coarse)[i] = reinterpret_cast<const uint32_t *>(k_srgbCoarse)[i];
+}
+
+__device__ __forceinline__ uint32_t srgbEncode(const SrgbTables &t, uint32_t S) // S <= 4 * 65535
+{
+    const uint32_t c = t.coarse[S >> 6];
+    return c + (S >= t.next[c] ? 1u : 0u);
+}
+
+// A coordinate that walks along a wrapped axis of n texels: `pos` is the coordinate itself (clamp), its place in the period n
+// (repeat) or in the period 2 n of there-and-back (mirror: ... 1 0 | 0 1 .. n-1 | n-1 .. 0 | 0 ...).  One division where the walk
+// starts, none per step.
+struct Walk
+{
+    int64_t pos;
+    uint32_t n, wrap;
+};
+
+__device__ __forceinline__ Walk walkFrom(int64_t i, uint32_t n, uint32_t wrap)
+{
+    Walk k = {i, n, wrap};
+    if (wrap != 0 && (i < 0 || i >= (int64_t)n))
+    {
+        const uint64_t p = wrap == kWrapMirror ? 2ull * n : (uint64_t)n;
+        k.pos = i >= 0 ? (int64_t)((uint64_t)i % p) : (int64_t)(p - 1u - ((uint64_t)(-i - 1) % p));
+    }
+    return k;
+}
+
+__device__ __forceinline__ uint32_t walkIndex(const Walk &k)
+{
+    if (k.wrap == kWrapMirror)
+        return static_cast<uint32_t>(k.pos < (int64_t)k.n ? k.pos : 2 * (int64_t)k.n - 1 - k.pos);
+    if (k.wrap == kWrapRepeat)
+        return static_cast<uint32_t>(k.pos);
+    return static_cast<uint32_t>(k.pos < 0 ? 0 : k.pos >= (int64_t)k.n ? (int64_t)k.n - 1 : k.pos);
+}
+
+__device__ __forceinline__ void walkStep(Walk &k)
+{
+    k.pos++;
+    if (k.wrap != 0 && k.pos == (k.wrap == kWrapMirror ? 2 * (int64_t)k.n : (int64_t)k.n))
+        k.pos = 0;
+}
+
+// the value channel c of a texel enters the sums with: c = 0..2 under the rule, c = 3 the byte of channel 3, c = 4..6 (NORMAL
+// only) the bytes of channels 0..2
+template <int KIND, int RULE>
+__device__ __forceinline__ int tapValue(const SrgbTables &t, uint32_t texel, int c)
+{
+    const uint32_t v = (texel >> (8 * (c & 3))) & 255u;
+    const int plain = KIND == kRGBA8Snorm ? static_cast<int>(static_cast<int8_t>(v)) : static_cast<int>(v);
+    if (c >= 3 || RULE == kPlain)
+        return plain;
+    if (RULE == kSrgb)
+        return t.lin[v];
+    return KIND == kRGBA8Snorm ? max(plain, -127) : 2 * plain - 255;
+}
+
+// The last step of the plain rule: clamp((s + 2^17) >> 18, 0..255 or -128..127), written as the clamp of the sum followed by the
+// shift (the same value: the shift is monotone).  Shift-then-clamp of two neighbouring channels is what the compiler turns into
+// v_ashr_pk_u8_i32, whose result it then ORs into the texel whole -- on the MI355X the upper half of that register kept what
+// it held before, and channel 2 and alpha of the texel came out wrong.
+template <int KIND>
+__device__ __forceinline__ uint32_t plainByte(int s) // s: the second pass's sum, 18 fraction bits
+{
+    const int t = s + (1 << 17);
+    if (KIND == kRGBA8Snorm)
+        return static_cast<uint32_t>(min(max(t, -(128 << 18)), (128 << 18) - 1) >> 18) & 255u;
+    return static_cast<uint32_t>(min(max(t, 0), (256 << 18) - 1)) >> 18;
+}
+
+template <int KIND, int RULE, int NTAPS, bool LAYERED>
+__global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
+                                                                  uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
+                                                                  uint32_t dstW, uint32_t dstH, size_t srcLayer, size_t dstLayer,
+                                                                  uint32_t wrap, uint32_t wide, uint32_t tilesY, MipTaps taps)
+{
+    constexpr int kRows = 2 * kTileY + NTAPS - 2; // source rows under a tile
+    constexpr int kWindow = NTAPS + 6;            // source texels (LDS rows) under four neighbouring outputs
+    constexpr int kLead = (1 - NTAPS / 2) & 3;    // texels between the 16-byte boundary and the window's first texel
+    constexpr int kChunks = (kLead + kWindow + 3) / 4;
+    constexpr int kSums = RULE == kNormal ? 7 : 4;
+    typedef typename std::conditional<RULE == kSrgb, int4, short4>::type Entry;
+    __shared__ Entry hbuf[kRows * kTileX];
+    __shared__ short4 pbuf[RULE == kNormal ? kRows * kTileX : 1]; // NORMAL: the plain h' of channels 0..2
+    __shared__ SrgbTables tables;                                 // (no LDS is allocated where it is not read)
+    if (LAYERED)
+    {
+        src += blockIdx.z * srcLayer;
+        dst += blockIdx.z * dstLayer;
+    }
+    if (RULE == kSrgb)
+    {
+        loadSrgbTables(tables);
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x;
+    const uint32_t x0 = blockIdx.x * kTileX;
+    const uint32_t groups = (min(dstW - x0, (uint32_t)kTileX) + 3u) / 4u; // groups of four output columns with a texel in them
+    for (uint32_t ty = blockIdx.y; ty < tilesY; ty += gridDim.y)
+    {
+        const uint32_t y0 = ty * kTileY;
+        const uint32_t tileH = min(dstH - y0, (uint32_t)kTileY);
+        const uint32_t rows = 2u * tileH + NTAPS - 2u;
+
+        // horizontal pass: item = (source row r of the tile, group g of four output columns)
+        for (uint32_t item = lane; item < rows * groups; item += 256u)
+        {
+            const uint32_t r = item / groups, g = item - r * groups;
+            const Walk wy = walkFrom(2 * (int64_t)y0 + 1 - NTAPS / 2 + (int64_t)r, srcH, wrap);
+            const uint8_t *row = src + (size_t)walkIndex(wy) * srcPitch;
+            const int64_t c0 = 2 * (int64_t)(x0 + 4u * g) + 1 - NTAPS / 2 - kLead; // a multiple of 4
+            uint32_t texel[4 * kChunks];
+            Walk wx = walkFrom(c0, srcW, wrap);
+#pragma unroll
+            for (int q = 0; q < kChunks; q++)
+            {
+                const int64_t c = c0 + 4 * q;
+                if (wide && c >= 0 && c + 4 <= (int64_t)srcW)
+                {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * c);
+                    texel[4 * q] = v.x;
+                    texel[4 * q + 1] = v.y;
+                    texel[4 * q + 2] = v.z;
+                    texel[4 * q + 3] = v.w;
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        walkStep(wx); // (inside the row the walk is at c itself, under every wrap)
+                }
+                else
+                {
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                    {
+                        texel[4 * q + e] = reinterpret_cast<const uint32_t *>(row)[walkIndex(wx)];
+                        walkStep(wx);
+                    }
+                }
+            }
+            int h[4][kSums];
+#pragma unroll
+            for (int c = 0; c < kSums; c++)
+            {
+                int v[kWindow];
+#pragma unroll
+                for (int i = 0; i < kWindow; i++)
+                    v[i] = tapValue<KIND, RULE>(tables, texel[kLead + i], c);
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                {
+                    int acc = 0;
+#pragma unroll
+                    for (int k = 0; k < NTAPS; k++)
+                        acc += __mul24(taps.w[k], v[2 * j + k]);
+                    h[j][c] = (RULE == kSrgb && c < 3) ? (acc + (1 << 13)) >> 14 : (acc + 512) >> 10;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+            {
+                const uint32_t at = r * kTileX + 4u * g + j;
+                if constexpr (RULE == kSrgb)
+                    hbuf[at] = make_int4(h[j][0], h[j][1], h[j][2], h[j][3]);
+                else
+                    hbuf[at] = make_short4((short)h[j][0], (short)h[j][1], (short)h[j][2], (short)h[j][3]);
+                if constexpr (RULE == kNormal)
+                    pbuf[at] = make_short4((short)h[j][4], (short)h[j][5], (short)h[j][6], 0);
+            }
+        }
+        __syncthreads();
+
+        // vertical pass: lane = (column x of the tile, rows 4 yg .. 4 yg + 3 of the tile)
+        const uint32_t x = lane & (kTileX - 1), yg = lane / kTileX;
+        if (x0 + x < dstW && 4u * yg < tileH)
+        {
+            int s[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    s[j][c] = 0;
+#pragma unroll
+            for (int i = 0; i < kWindow; i++)
+            {
+                const Entry e = hbuf[(8u * yg + i) * kTileX + x];
+                const int ev[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (i - 2 * j >= 0 && i - 2 * j < NTAPS)
+                    {
+#pragma unroll
+                        for (int c = 0; c < 4; c++)
+                            s[j][c] += __mul24(taps.w[i - 2 * j], ev[c]);
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+            {
+                uint32_t out = plainByte<KIND>(s[j][3]) << 24;
+                if (RULE == kPlain)
+                {
+#pragma unroll
+                    for (int c = 0; c < 3; c++)
+                        out |= plainByte<KIND>(s[j][c]) << (8 * c);
+                }
+                else if (RULE == kSrgb)
+                {
+#pragma unroll
+                    for (int c = 0; c < 3; c++)
+                        out |= srgbEncode(tables, static_cast<uint32_t>(min(max((s[j][c] + (1 << 11)) >> 12, 0), 4 * 65535))) << (8 * c);
+                }
+                else
+                {
+                    const int S[3] = {(s[j][0] + 128) >> 8, (s[j][1] + 128) >> 8, (s[j][2] + 128) >> 8};
+                    if ((S[0] | S[1] | S[2]) == 0)
+                    {
+                        int p[3] = {0, 0, 0};
+#pragma unroll
+                        for (int k = 0; k < NTAPS; k++)
+                        {
+                            const short4 e = pbuf[(8u * yg + 2 * j + k) * kTileX + x];
+                            p[0] += __mul24(taps.w[k], e.x);
+                            p[1] += __mul24(taps.w[k], e.y);
+                            p[2] += __mul24(taps.w[k], e.z);
+                        }
+#pragma unroll
+                        for (int c = 0; c < 3; c++)
+                            out |= plainByte<KIND>(p[c]) << (8 * c);
+                    }
+                    else
+                    {
+                        const float fx = static_cast<float>(S[0]), fy = static_cast<float>(S[1]), fz = static_cast<float>(S[2]);
+                        const float f[3] = {fx, fy, fz};
+                        const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
+#pragma unroll
+                        for (int c = 0; c < 3; c++)
+                        {
+                            const float q = f[c] / len;
+                            const int r = KIND == kRGBA8Snorm ? min(max(static_cast<int>(floorf(q * 127.0f + 0.5f)), -127), 127)
+                                                              : min(max(static_cast<int>(floorf(q * 127.5f + 128.0f)), 0), 255);
+                            out |= (static_cast<uint32_t>(r) & 255u) << (8 * c);
+                        }
+                    }
+                }
+                if (4u * yg + j < tileH)
+                    reinterpret_cast<uint32_t *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = out;
+            }
+        }
+        __syncthreads(); // the next tile's horizontal pass rewrites the entries
+    }
+}
+
+template <int KIND, int RULE, int NTAPS, bool LAYERED>
+hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps, hipStream_t stream)
+{
+    const uint32_t dstW = m.srcW > 1u ? m.srcW >> 1 : 1u, dstH = m.srcH > 1u ? m.srcH >> 1 : 1u;
+    // 16-byte reads: the first row and the pitch (and, for layers, the layer stride) on 16-byte boundaries -- the test of mipLaunchShape on
+    // the source alone; the output is written a texel at a time
+    uintptr_t bits = reinterpret_cast<uintptr_t>(m.src) | m.srcPitch;
+    if (m.layers > 1u)
+        bits |= m.srcLayer;
+    const uint32_t wide = (bits & 15u) == 0 ? 1u : 0u;
+    const uint32_t tilesY = (dstH + kTileY - 1u) / kTileY;
+    const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers ? m.layers : 1u);
+    hipLaunchKernelGGL((cvttmi_mipresample_kernel<KIND, RULE, NTAPS, LAYERED>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
+                       (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, taps);
+    return hipGetLastError();
+}
+
+template <int KIND, int RULE, bool LAYERED>
+hipError_t resampleByTaps(const MipLayers &m, uint32_t wrap, const MipTaps &taps, uint32_t count, hipStream_t stream)
+{
+    switch (count)
+    {
+    case 4: return launchResample<KIND, RULE, 4, LAYERED>(m, wrap, taps, stream);
+    case 8: return launchResample<KIND, RULE, 8, LAYERED>(m, wrap, taps, stream);
+    case 12: return launchResample<KIND, RULE, 12, LAYERED>(m, wrap, taps, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL; anything else is hipErrorInvalidValue
+template <bool LAYERED>
+hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
+{
+    if (m.srcW == 0 || m.srcH == 0)
+        return hipSuccess;
+    if (!taps || count > 12u || (wrap != 0 && wrap != kWrapRepeat && wrap != kWrapMirror))
+        return hipErrorInvalidValue;
+    MipTaps t;
+    for (uint32_t k = 0; k < 12u; k++)
+        t.w[k] = k < count ? taps[k] : 0;
+    if (kind == kRGBA8 && rule == kPlain)
+        return resampleByTaps<kRGBA8, kPlain, LAYERED>(m, wrap, t, count, stream);
+    if (kind == kRGBA8 && rule == kSrgb)
+        return resampleByTaps<kRGBA8, kSrgb, LAYERED>(m, wrap, t, count, stream);
+    if (kind == kRGBA8 && rule == kNormal)
+        return resampleByTaps<kRGBA8, kNormal, LAYERED>(m, wrap, t, count, stream);
+    if (kind == kRGBA8Snorm && rule == kPlain)
+        return resampleByTaps<kRGBA8Snorm, kPlain, LAYERED>(m, wrap, t, count, stream);
+    if (kind == kRGBA8Snorm && rule == kNormal)
+        return resampleByTaps<kRGBA8Snorm, kNormal, LAYERED>(m, wrap, t, count, stream);
+    return hipErrorInvalidValue;
+}
+} // namespace
+
+// One level under a mip kernel: `rule` = CVTTMI_MIP_FILTER_BOX (the plain rule), _SRGB or _NORMAL, `wrap` = 0 or one
+// CVTTMI_MIP_WRAP_* flag, taps[0 .. count - 1] the kernel's Q14 table (count = 4, 8 or 12)
+extern "C" hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
+                                             int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
+{
+    return resampleByKind<false>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, 0, 0, 0}, kind, rule, wrap, taps, count, stream);
+}
+
+// ... and the same level of `layers` images, the layer in the grid's z
+extern "C" hipError_t cvttmi_launch_resample_layered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
+                                                     size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule,
+                                                     uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
+{
+    if (layers == 0 || layers > kMipMaxLayers)
+        return hipErrorInvalidValue;
+    return resampleByKind<true>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, taps, count,
+                                stream);
+}

@@ -1,6 +1,6 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-alphaweight] [-srgb] [-metrics] [-array | -cube] input [input ...] output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-mipkernel triangle|mitchell|lanczos3|kaiser] [-wrap clamp|repeat|mirror] [-alphaweight] [-srgb] [-metrics] [-array | -cube] input [input ...] output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
@@ -16,6 +16,9 @@ unchanged, then one line per further level: its PSNR over the format's channels 
 R11, which has no image form.
 -mipfilter box|srgb|normal, -alphaweight: the filter of the chain (Context.build_mips: "srgb" averages colour in linear light,
 "normal" renormalises a normal map, -alphaweight weights colour by alpha -- with box or srgb); either implies -mips.
+-mipkernel triangle|mitchell|lanczos3|kaiser: every level is filtered with that kernel (4, 8 or 12 taps per direction) instead of the
+2x2 rule, under -mipfilter box (the default), srgb or normal; implies -mips.  Not with -alphaweight, not for bc6h.  -wrap
+clamp|repeat|mirror: how the kernel's taps leave the image (repeat: a tiling texture); only with -mipkernel.
 -srgb: the file carries the sRGB code of its format (container.SRGB_FORMATS).  Only a mark: level 0 and the encode are unchanged.
 -array: every input is one layer of a texture array (N inputs, then the output); -cube: the inputs are the faces of a cube in the
 order +X -X +Y -Y +Z -Z, or of a cube array (6 n inputs).  Either also takes a single .npy of shape (L, H, W, 4).  All layers
@@ -72,22 +75,23 @@ def encode_file(image, fmt, options=None, plan=None, ctx=None):
     return packed.cpu().numpy()
 
 
-def encode_file_mips(image, fmt, options=None, plan=None, ctx=None, mip_filter="box"):
+def encode_file_mips(image, fmt, options=None, plan=None, ctx=None, mip_filter="box", kernel=None, wrap="clamp"):
     """(H, W, 4) uint8 numpy image -> [packed blocks of level L], the full chain, container order (not R11)"""
     import torch
     ctx = ctx or api.default_context()
-    levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan, mip_filter=mip_filter)
+    levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan, mip_filter=mip_filter,
+                             kernel=kernel, wrap=wrap)
     torch.cuda.synchronize(ctx.device)
     return [level.cpu().numpy() for level in levels]
 
 
-def measure_file_mips(image, fmt, levels, ctx=None, mip_filter="box"):
+def measure_file_mips(image, fmt, levels, ctx=None, mip_filter="box", kernel=None, wrap="clamp"):
     """[ErrorReport of level L against its own image] for the levels encode_file_mips returned, level 0 left out"""
     import torch
     ctx = ctx or api.default_context()
     fmt = container.canonical(fmt)
     images = ctx.build_mips(torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device), len(levels), signed=fmt in ("bc4s", "bc5s"),
-                            filter=mip_filter)
+                            filter=mip_filter, kernel=kernel, wrap=wrap)
     return [ctx.measure_image(fmt, img, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
             for img, packed in zip(images[1:], levels[1:])]
 
@@ -131,12 +135,13 @@ def load_layers(paths):
     return np.stack(images)
 
 
-def encode_file_texture(images, fmt, options=None, plan=None, ctx=None, mips=False, mip_filter="box", order="level"):
+def encode_file_texture(images, fmt, options=None, plan=None, ctx=None, mips=False, mip_filter="box", order="level", kernel=None,
+                        wrap="clamp"):
     """(L, H, W, 4) uint8 numpy layers -> [layer][level] packed blocks (numpy), one level or the full chain (not R11)"""
     import torch
     ctx = ctx or api.default_context()
     blocks = ctx.encode_texture(container.canonical(fmt), torch.from_numpy(images).cuda(ctx.device), options, plan,
-                                levels=None if mips else 1, order=order, mip_filter=mip_filter)
+                                levels=None if mips else 1, order=order, mip_filter=mip_filter, kernel=kernel, wrap=wrap)
     torch.cuda.synchronize(ctx.device)
     host, start = blocks.base.cpu().numpy(), blocks.base.data_ptr()
     per = host.shape[1]
@@ -163,6 +168,7 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     fmt, uniform, fake, quality, dds, metrics, mips, paths = "etc2rgb", False, False, None, False, False, False, []
     mip_filter, alpha_weight, srgb, array, cube = None, False, False, False, False
+    mip_kernel, wrap = None, None
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -183,6 +189,12 @@ def main(argv=None):
         elif a == "-mipfilter" and i + 1 < len(argv) and argv[i + 1] in ("box", "srgb", "normal"):
             mip_filter = argv[i + 1]
             i += 1
+        elif a == "-mipkernel" and i + 1 < len(argv) and argv[i + 1] in api.MIP_KERNELS:
+            mip_kernel = argv[i + 1]
+            i += 1
+        elif a == "-wrap" and i + 1 < len(argv) and argv[i + 1] in api.MIP_WRAPS:
+            wrap = argv[i + 1]
+            i += 1
         elif a == "-alphaweight":
             alpha_weight = True
         elif a == "-srgb":
@@ -202,12 +214,18 @@ def main(argv=None):
     if (array and cube) or len(paths) < 2 or (len(paths) != 2 and not (array or cube)):
         sys.stderr.write(USAGE + "\n")
         return 2
-    mips = mips or mip_filter is not None or alpha_weight
+    mips = mips or mip_filter is not None or alpha_weight or mip_kernel is not None
     mip_filter = (mip_filter or "box") + ("+alpha" if alpha_weight else "")
     try:
         fmt = container.canonical(fmt)
         if mip_filter not in api.MIP_FILTERS:
             raise ValueError("-alphaweight goes with -mipfilter box or srgb")
+        if mip_kernel is not None and alpha_weight:
+            raise ValueError("-mipkernel does not go with -alphaweight")
+        if mip_kernel is not None and fmt in ("bc6hu", "bc6hs"):
+            raise ValueError("-mipkernel: %s is encoded from half-float images, which take the 2x2 rule only" % fmt)
+        if wrap is not None and mip_kernel is None:
+            raise ValueError("-wrap goes with -mipkernel")
         if fmt in ("bc4s", "bc5s") and mip_filter not in ("box", "normal"):
             raise ValueError("-mipfilter %s: %s averages the image as int8, which takes box or normal" % (mip_filter, fmt))
         if srgb and fmt not in container.SRGB_FORMATS:
@@ -229,6 +247,7 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         sys.stderr.write("%s\n" % e)
         return 1
+    how = dict(mip_filter=mip_filter, kernel=mip_kernel, wrap=wrap or "clamp")
     options = api.Options()
     if uniform:  # etc2packer.cpp:202-205
         options.flags |= api.Flags.Uniform
@@ -240,17 +259,17 @@ def main(argv=None):
         api.ConfigureBC7EncodingPlanFromQuality(plan, quality)
     if array or cube:
         h, w = layers.shape[1:3]
-        texture = encode_file_texture(layers, fmt, options, plan, mips=mips, mip_filter=mip_filter, order="layer" if dds else "level")
+        texture = encode_file_texture(layers, fmt, options, plan, mips=mips, order="layer" if dds else "level", **how)
         (container.write_dds_texture if dds else container.write_ktx_texture)(paths[-1], fmt, w, h, texture, cube, srgb)
         for n, (image, levels) in enumerate(zip(layers, texture) if metrics else ()):
             sys.stdout.write("layer %d\n" % n)
             print_metrics(measure_file(image, fmt, levels[0], options))
             if mips:
-                print_mip_metrics(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), w, h)
+                print_mip_metrics(measure_file_mips(image, fmt, levels, **how), w, h)
         return 0
     h, w = image.shape[:2]
     if mips:
-        levels = encode_file_mips(image, fmt, options, plan, mip_filter=mip_filter)
+        levels = encode_file_mips(image, fmt, options, plan, **how)
         packed = levels[0]
         (container.write_dds_mips if dds else container.write_ktx_mips)(paths[1], fmt, w, h, levels, srgb)
     else:
@@ -259,7 +278,7 @@ def main(argv=None):
     if metrics:
         print_metrics(measure_file(image, fmt, packed, options))
         if mips:
-            print_mip_metrics(measure_file_mips(image, fmt, levels, mip_filter=mip_filter), w, h)
+            print_mip_metrics(measure_file_mips(image, fmt, levels, **how), w, h)
     return 0
 
 

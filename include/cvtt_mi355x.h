@@ -350,6 +350,38 @@ int cvttmi_compact_rows_device(cvttmi_context *ctx, void *d_out, const void *d_p
  * RGBA8 takes every filter above, RGBA8_SNORM takes BOX and NORMAL, RGBA16F takes BOX; NORMAL | ALPHA_WEIGHTED and every other
  * value are rejected (CVTTMI_E_INVALID with an error text, nothing written).  Otherwise the call is cvttmi_build_mips_device:
  * the same checks, one launch per level, exactly the levels' bytes written.
+ * Mip kernels and wrap modes.  The `filter` word of the calls below has two more fields: a kernel in bits 4-7 (0: the 2x2 rules
+ * above, untouched) and a wrap mode in bits 9-10.  Under a kernel the geometry, the rounded levels, the layout and the launch per
+ * level stay; only the footprint of an output texel grows from 2x2 to n x n source texels, n = 4 R taps per direction:
+ *   CVTTMI_MIP_KERNEL_TRIANGLE  R = 1  1 - |t|                     CVTTMI_MIP_KERNEL_LANCZOS3  R = 3  sinc(t) sinc(t / 3)
+ *   CVTTMI_MIP_KERNEL_MITCHELL  R = 2  Mitchell-Netravali B = C = 1/3   CVTTMI_MIP_KERNEL_KAISER  R = 3  sinc(t) I0(4 sqrt(1 - (t/3)^2)) / I0(4)
+ * Output column x is centred between source columns 2x and 2x + 1; tap k = 0 .. n - 1 reads source column 2x + 1 - 2R + k, wrapped
+ * (rows alike), and sits t_k = (k - n/2 + 0.5) / 2 destination texels from the centre -- the same for every output texel, so a
+ * kernel is ONE table w[0 .. n-1] (tools/gen_mip_kernels.py, cvttmi_mip_kernel_taps): the float64 weights divided by their sum,
+ * each quantised as floor(16384 w + 0.5), what is missing to 16384 split equally between the two central taps:
+ *   triangle  2048 6144 6144 2048                                                      sum |w| = 16384
+ *   mitchell  -121 -192 2098 6407 6407 2098 -192 -121                                  sum |w| = 17636
+ *   lanczos3  60 247 -557 -1092 2220 7314 7314 2220 -1092 -557 247 60                  sum |w| = 22980
+ *   kaiser    103 266 -556 -1076 2195 7260 7260 2195 -1076 -556 266 103                sum |w| = 22912
+ * An odd last column / row is no longer dropped (it is read as a neighbour); a dimension that is already 1 reproduces itself.
+ * Wrap: 0 clamps a coordinate to the edge; CVTTMI_MIP_WRAP_REPEAT takes it modulo the size; CVTTMI_MIP_WRAP_MIRROR reflects with
+ * the edge texel repeated once (-1 -> 0, w -> w - 1, period 2 w), correct however many times the footprint exceeds the image.
+ * Arithmetic: two passes, horizontal then vertical, int32 throughout, arithmetic shifts; no intermediate is clamped.
+ *   plain rule (CVTTMI_MIP_FILTER_BOX under a kernel; channel 3 always), v = the byte as uint8 / int8:
+ *       h = sum w_k v_k;  h' = (h + 512) >> 10  (four fraction bits, |h'| <= 5723);  s = sum w_j h'_j;
+ *       out = clamp((s + 2^17) >> 18, 0..255 or -128..127)
+ *   CVTTMI_MIP_FILTER_SRGB, channels 0..2, v = T[byte]:  h' = (h + 2^13) >> 14;  s = sum w_j h'_j;
+ *       S = clamp((s + 2^11) >> 12, 0, 4 * 65535);  out = encode(S) as above.  (|h| <= 1.51e9, |s| <= 1.6e9: below 2^31.)
+ *   CVTTMI_MIP_FILTER_NORMAL, channels 0..2: the plain two passes on X (as above) up to s_c;  S_c = (s_c + 2^7) >> 8 (10 fraction bits,
+ *       |S_c| < 2^20: exact as a float).  All three S_c zero: the plain rule on the three channels' bytes.  Otherwise, in IEEE single
+ *       precision, every operation rounded on its own: len = sqrtf((fx * fx + fy * fy) + fz * fz), q = fS_c / len, and the two
+ *       re-encode formulas above applied to q.
+ * With a kernel RGBA8 takes BOX, SRGB and NORMAL, RGBA8_SNORM BOX and NORMAL, under any one wrap mode.  CVTTMI_E_INVALID with an
+ * error text, nothing queued, nothing written: a kernel with RGBA16F (a kernel with negative lobes rings below zero in HDR data:
+ * what to do there is a decision of its own) or with ALPHA_WEIGHTED (the weighted mean's denominator can turn negative: likewise),
+ * a wrap flag without a kernel, both wrap flags, an unknown kernel code.
+ * cvttmi_mip_kernel_taps: host only, no context.  Copies the table of the word's kernel to taps[0 .. 11] (zeros beyond *count = n);
+ * CVTTMI_E_INVALID for kernel 0, an unknown kernel or a NULL pointer.
  * cvttmi_srgb_tables: host only, no context.  Copies T and U (U[k] at thresholds[k - 1]); CVTTMI_E_INVALID for a NULL pointer.
  * cvttmi_mip_layout: host only, no context.  Fills out[0 .. levels - 1] with each level's place in three buffers, and
  * out[levels] (so `out` has levels + 1 entries) with their ends = the three total sizes:
@@ -390,10 +422,17 @@ int cvttmi_build_mips_device(cvttmi_context *ctx, void *d_pyramid, size_t pyrami
 #define CVTTMI_MIP_FILTER_SRGB 1
 #define CVTTMI_MIP_FILTER_NORMAL 2
 #define CVTTMI_MIP_FILTER_ALPHA_WEIGHTED 0x100 /* a flag, OR-ed onto BOX or SRGB */
+#define CVTTMI_MIP_KERNEL_TRIANGLE 0x10 /* bits 4-7: a kernel, OR-ed onto BOX, SRGB or NORMAL; 0 = the 2x2 rule */
+#define CVTTMI_MIP_KERNEL_MITCHELL 0x20
+#define CVTTMI_MIP_KERNEL_LANCZOS3 0x30
+#define CVTTMI_MIP_KERNEL_KAISER 0x40
+#define CVTTMI_MIP_WRAP_REPEAT 0x200 /* bits 9-10: how a kernel's taps leave the image; 0 = clamp to the edge */
+#define CVTTMI_MIP_WRAP_MIRROR 0x400
 int cvttmi_build_mips_filtered_device(cvttmi_context *ctx, void *d_pyramid, size_t pyramidBytes, const void *d_image, uint32_t width,
                                       uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, uint32_t filter,
                                       void *hipStream);
 int cvttmi_srgb_tables(uint16_t toLinear[256], uint32_t thresholds[255]);
+int cvttmi_mip_kernel_taps(uint32_t filter, int16_t taps[12], uint32_t *count);
 
 /* ---- texture arrays and cube maps (not part of the reference's API) ----
  * A texture is `layers` images of one size, each with `levels` mip levels; layers = array elements x faces.  A cube is 6 layers
