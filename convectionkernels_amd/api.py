@@ -1033,9 +1033,17 @@ class Context:
             raise CvttError("image must be RGBA8 or RGBA16F")
         return image if image.stride(2) == 1 and image.stride(1) == 4 else image.contiguous()
 
+    def _one_layer(self, image):
+        """the (H, W, 4) image of build_mips / encode_mips as a (1, H, W, 4) view, never a copy of its rows: a row stride the
+        single-image C entry refuses (below the row, or no whole texels) is refused here as it was there"""
+        image = self._image_in(image)
+        if image.stride(0) < 4 * image.shape[1] or image.stride(0) % 4:
+            raise CvttError("image rows must be whole texels and at least a row apart")
+        return image[None]
+
     # -- mip chains: 2x2 filter on the device, and the whole chain through one encode call --
     def build_mips(self, image, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
-        """(H,W,4) CUDA image -> the list of its mip levels (cvttmi_build_mips_device): [0] is the image itself, the others are
+        """(H,W,4) CUDA image -> the list of its mip levels (build_mips_array of one layer): [0] is the image itself, the others are
         (h_L, w_L, 4) views of the image's dtype into ONE allocation laid out by mip_layout.  Level L+1 is max(1, w_L >> 1) x
         max(1, h_L >> 1), a 2x2 box of the rounded level L (an odd last row / column is dropped).  uint8: (a+b+c+d+2) >> 2;
         int8, or signed=True (the bytes BC4S / BC5S read): the same on int8 with an arithmetic shift; a 2-byte dtype: RGBA16F,
@@ -1047,49 +1055,27 @@ class Context:
         that kernel's 4 / 8 / 12 taps per direction instead, under "box" (the plain rule), "srgb" or "normal", uint8 or int8
         images; an odd last row / column is then read as a neighbour.  wrap: how the taps leave the image: "clamp", "repeat" (a
         tiling texture) or "mirror"; only with a kernel."""
-        import torch
-        image = self._image_in(image)
-        h, w = int(image.shape[0]), int(image.shape[1])
-        esz = image.element_size()
-        if esz == 2 and signed:
-            raise CvttError("signed selects the int8 rule of an RGBA8 image")
-        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or image.dtype == torch.int8) else PIXELS_RGBA8
-        layout = mip_layout(w, h, 4 * esz, 16, levels)
-        pyramid = torch.empty(layout.pyramid_bytes, dtype=torch.uint8, device=image.device)
-        stream = self._stream(stream, image.device)
-        self._check(self._lib.cvttmi_build_mips_filtered_device(self._h, pyramid.data_ptr(), layout.pyramid_bytes, image.data_ptr(), w, h,
-                                                                image.stride(0) * esz, kind, len(layout), mip_filter_word(filter, kernel, wrap),
-                                                                ctypes.c_void_p(stream)), "build_mips")
-        return [image] + [pyramid[L.byteOffset: L.byteOffset + L.rowPitchBytes * L.height].view(image.dtype).view(L.height, L.width, 4)
-                          for L in layout[1:]]
+        return self.build_mips_array(self._one_layer(image), levels, signed, stream, filter, kernel, wrap)[0]
 
     def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box", kernel=None, wrap="clamp"):
         """(H,W,4) CUDA image -> the packed blocks of every mip level: a list of (ceil(w_L/4) * ceil(h_L/4), bytes per block)
-        uint8 views, level 0 first, consecutive in one allocation (container order).  Level L equals
+        uint8 views, level 0 first, consecutive in one allocation (container order): encode_texture of one layer.  Level L equals
         encode_image(fmt, build_mips(image)[L]) byte for byte; the levels are tiled into one block tensor and searched by ONE
         encode call (groups of eight blocks are independent), so the small levels cost no launches of their own.  fmt as for
         encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain.  mip_filter: build_mips's
         `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L]); kernel, wrap:
-        build_mips's, and the same holds under them."""
+        build_mips's, and the same holds under them.
+        The averaging rule follows the format, so an int8 image is taken by "bc4s" / "bc5s" alone: with any other format it is a
+        CvttError (it was one for "bc7" before; the other formats used to average it as int8 and encode the bytes).
+        The levels are views of the allocation that also holds the call's work space (pyramids, tiles, padded blocks: several
+        times the blocks' size), so that kernels on a caller's own stream never outlive it: any level kept keeps all of it.
+        Copy (clone) the levels to keep for long."""
         import torch
         if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
-        _, bpb, _, _ = TEXTURE_FORMATS[fmt]
-        images = self.build_mips(image, levels, signed=fmt in ("bc4s", "bc5s"), stream=stream, filter=mip_filter, kernel=kernel, wrap=wrap)
-        image = images[0]
-        esz = image.element_size()
-        layout = mip_layout(int(image.shape[1]), int(image.shape[0]), 4 * esz, bpb, len(images))
-        sp = ctypes.c_void_p(self._stream(stream, image.device))
-        blocks = torch.empty((layout.tile_count, 16, 4), dtype=image.dtype, device=image.device)
-        for L, img in zip(layout, images):
-            self._check(self._lib.cvttmi_tile_image_device(self._h, blocks[L.firstTile:].data_ptr(), img.data_ptr(), L.width, L.height,
-                                                           img.stride(0) * esz, 0 if esz == 1 else 1, sp), "tile_image")
-        packed = self.encode(fmt, blocks, options, plan, stream=stream)
-        out = torch.empty((layout.block_count, bpb), dtype=torch.uint8, device=image.device)
-        for L in layout:
-            self._check(self._lib.cvttmi_compact_rows_device(self._h, out[L.firstBlock:].data_ptr(), packed[L.firstTile:].data_ptr(),
-                                                             L.width, L.height, bpb, sp), "compact_rows")
-        return [out[L.firstBlock: L.firstBlock + L.blockCount] for L in layout]
+        if isinstance(image, torch.Tensor) and image.dtype == torch.int8 and fmt not in ("bc4s", "bc5s"):
+            raise CvttError("%s is not encoded from an int8 image (bc4s / bc5s are)" % fmt)
+        return self.encode_texture(fmt, self._one_layer(image), options, plan, levels, "layer", mip_filter, stream, kernel, wrap)[0]
 
     # -- texture arrays and cube maps: `layers` images of one size through mips and encode at once (cvtt_mi355x.h) --
     def _images_in(self, images):
@@ -1119,8 +1105,8 @@ class Context:
         return images, row * esz, layer * esz
 
     def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
-        """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): build_mips
-        for every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
+        """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): the mip
+        chain of every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
         into one allocation: layer l's chain as mip_layout places it, texture_layout's pyramidLayerBytes apart.  levels, signed,
         filter, kernel, wrap: as for build_mips."""
         import torch
@@ -1148,7 +1134,9 @@ class Context:
         in the order +X -X +Y -Y +Z -Z -> TextureBlocks: [layer][level] packed blocks, uint8 views into ONE allocation (.base) in
         `order`: "layer" = every layer's chain consecutive (DDS), "level" = every level's layers consecutive (KTX).  One C call
         (cvttmi_encode_texture_device): the mips of all layers a launch per level, one tile launch, one search, one compact launch.
-        [l][L] equals encode_mips(fmt, images[l], ..)[L] byte for byte.  fmt, levels, mip_filter, kernel, wrap: as for encode_mips."""
+        [l][L] equals encode_image(fmt, build_mips_array(images, ..)[l][L]) byte for byte.  fmt, levels, mip_filter, kernel, wrap: as for
+        encode_mips.  The allocation behind .base also holds the call's work space (texture_layout's workBytes, several times the
+        blocks), so any view kept keeps that too: clone what is kept for long."""
         import torch
         if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
@@ -1164,8 +1152,11 @@ class Context:
         levels = mip_level_count(w, h) if levels is None else int(levels)
         ov = order_value(order)
         sizes = texture_layout(w, h, 4 * esz, bpb, levels, n, ov)
-        out = torch.empty((sizes.blocks, bpb), dtype=torch.uint8, device=images.device)
-        work = torch.empty(sizes.workBytes, dtype=torch.uint8, device=images.device)
+        # blocks and work space in one allocation: every view of the blocks (.base among them) keeps the work space alive, which the
+        # kernels of a caller's own stream may still be using
+        out_bytes = sizes.blocks * bpb
+        both = torch.empty(-(-out_bytes // 256) * 256 + sizes.workBytes, dtype=torch.uint8, device=images.device)
+        out, work = both[:out_bytes].view(sizes.blocks, bpb), both[both.numel() - sizes.workBytes:]
         self._check(self._lib.cvttmi_encode_texture_device(self._h, fid, out.data_ptr(), sizes.blocks * bpb, images.data_ptr(), w, h, row_pitch,
                                                            layer_pitch, n, levels, mip_filter_word(mip_filter, kernel, wrap), ov,
                                                            ctypes.addressof(options),
@@ -1174,7 +1165,6 @@ class Context:
                     "encode_texture(%s)" % fmt)
         res = TextureBlocks()
         res.base, res.order = out, "level" if ov == ORDER_LEVEL_MAJOR else "layer"
-        res.work = work  # kept as long as the result: on a caller's own stream the kernels may still be using it
         # one strided view per level over all layers, then its n slices: a few tensor operations per level, not per subresource
         per_level = [out.as_strided((n, count, bpb), (step * bpb, bpb, 1), first * bpb).unbind(0)
                      for first, step, count in _texture_places(w, h, 4 * esz, bpb, levels, n, ov)]

@@ -29,8 +29,8 @@ __device__ __forceinline__ uint32_t box4x8(uint32_t a, uint32_t b, uint32_t c, u
     return (((even >> 2) & m) | (((odd >> 2) & m) << 8)) ^ bias;
 }
 
-// What one level's launch reads and writes: one image (layers == 0), or the same level of `layers` images of a texture array,
-// srcLayer / dstLayer bytes apart, layer z in workgroups z of the grid.
+// What one level's launch reads and writes: the same level of `layers` images (1 .. kMipMaxLayers; one image is a texture array of
+// one layer), srcLayer / dstLayer bytes apart, layer z in workgroups z of the grid.
 struct MipLayers
 {
     const void *src;
@@ -74,7 +74,7 @@ inline MipLaunch mipLaunchShape(const MipLayers &m, uint32_t texel)
     const uint32_t by = 256u / bx;
     const uint32_t gy = (L.dstH + by - 1u) / by;
     L.block = dim3(bx, by);
-    L.grid = dim3((L.perRow + bx - 1u) / bx, gy < 1024u ? gy : 1024u, m.layers ? m.layers : 1u);
+    L.grid = dim3((L.perRow + bx - 1u) / bx, gy < 1024u ? gy : 1024u, m.layers);
     return L;
 }
 } // namespace

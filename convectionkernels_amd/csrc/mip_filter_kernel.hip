@@ -115,18 +115,15 @@ __device__ __forceinline__ uint32_t filterTexel(const SrgbTables &t, uint32_t a,
     return out;
 }
 
-// One output texel per lane: cvttmi_downsample_narrow_kernel with a filter.
-template <int KIND, int FILTER, bool LAYERED>
+// One output texel per lane: cvttmi_downsample_narrow_kernel with a filter (the layer in the grid's z there and here).
+template <int KIND, int FILTER>
 __global__ void __launch_bounds__(256) cvttmi_mipfilter_narrow_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                        uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW,
                                                                        uint32_t srcH, uint32_t dstW, uint32_t dstH, size_t srcLayer,
                                                                        size_t dstLayer)
 {
-    if (LAYERED)
-    {
-        src += blockIdx.z * srcLayer;
-        dst += blockIdx.z * dstLayer;
-    }
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
     __shared__ SrgbTables tables; // (no LDS is allocated where it is not read)
     if (FILTER & kSrgb)
         loadSrgbTables(tables);
@@ -143,16 +140,13 @@ __global__ void __launch_bounds__(256) cvttmi_mipfilter_narrow_kernel(const uint
 }
 
 // Four output texels per lane, 16-byte accesses: cvttmi_downsample_wide_kernel with a filter (no clamp in x or y).
-template <int KIND, int FILTER, bool LAYERED>
+template <int KIND, int FILTER>
 __global__ void __launch_bounds__(256) cvttmi_mipfilter_wide_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                      uint8_t *__restrict__ dst, size_t dstPitch, uint32_t chunks,
                                                                      uint32_t dstH, size_t srcLayer, size_t dstLayer)
 {
-    if (LAYERED)
-    {
-        src += blockIdx.z * srcLayer;
-        dst += blockIdx.z * dstLayer;
-    }
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
     __shared__ SrgbTables tables;
     if (FILTER & kSrgb)
         loadSrgbTables(tables);
@@ -173,54 +167,46 @@ __global__ void __launch_bounds__(256) cvttmi_mipfilter_wide_kernel(const uint8_
     }
 }
 
-template <int KIND, int FILTER, bool LAYERED>
+template <int KIND, int FILTER>
 hipError_t launchFiltered(const MipLayers &m, hipStream_t stream)
 {
     const MipLaunch L = mipLaunchShape(m, 4u);
     if (L.wide)
-        hipLaunchKernelGGL((cvttmi_mipfilter_wide_kernel<KIND, FILTER, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src,
+        hipLaunchKernelGGL((cvttmi_mipfilter_wide_kernel<KIND, FILTER>), L.grid, L.block, 0, stream, (const uint8_t *)m.src,
                            m.srcPitch, (uint8_t *)m.dst, m.dstPitch, L.perRow, L.dstH, m.srcLayer, m.dstLayer);
     else
-        hipLaunchKernelGGL((cvttmi_mipfilter_narrow_kernel<KIND, FILTER, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src,
+        hipLaunchKernelGGL((cvttmi_mipfilter_narrow_kernel<KIND, FILTER>), L.grid, L.block, 0, stream, (const uint8_t *)m.src,
                            m.srcPitch, (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, L.dstW, L.dstH, m.srcLayer, m.dstLayer);
     return hipGetLastError();
 }
 
 // RGBA8 takes SRGB, NORMAL, BOX | ALPHA_WEIGHTED and SRGB | ALPHA_WEIGHTED, RGBA8_SNORM takes NORMAL; anything else is
 // hipErrorInvalidValue
-template <bool LAYERED>
 hipError_t filteredByKind(const MipLayers &m, int kind, uint32_t filter, hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
     if (kind == kRGBA8Snorm && filter == kNormal)
-        return launchFiltered<kRGBA8Snorm, kNormal, LAYERED>(m, stream);
+        return launchFiltered<kRGBA8Snorm, kNormal>(m, stream);
     if (kind != kRGBA8)
         return hipErrorInvalidValue;
     switch (filter)
     {
-    case kSrgb: return launchFiltered<kRGBA8, kSrgb, LAYERED>(m, stream);
-    case kNormal: return launchFiltered<kRGBA8, kNormal, LAYERED>(m, stream);
-    case kAlphaWeighted: return launchFiltered<kRGBA8, kAlphaWeighted, LAYERED>(m, stream);
-    case kSrgb | kAlphaWeighted: return launchFiltered<kRGBA8, kSrgb | kAlphaWeighted, LAYERED>(m, stream);
+    case kSrgb: return launchFiltered<kRGBA8, kSrgb>(m, stream);
+    case kNormal: return launchFiltered<kRGBA8, kNormal>(m, stream);
+    case kAlphaWeighted: return launchFiltered<kRGBA8, kAlphaWeighted>(m, stream);
+    case kSrgb | kAlphaWeighted: return launchFiltered<kRGBA8, kSrgb | kAlphaWeighted>(m, stream);
     default: return hipErrorInvalidValue;
     }
 }
 } // namespace
 
 // cvttmi_launch_downsample under a filter other than the box (the shim sends CVTTMI_MIP_FILTER_BOX there)
-extern "C" hipError_t cvttmi_launch_downsample_filtered(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW,
-                                                        uint32_t srcH, int kind, uint32_t filter, hipStream_t stream)
-{
-    return filteredByKind<false>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, 0, 0, 0}, kind, filter, stream);
-}
-
-// ... and cvttmi_launch_downsample_layered under such a filter
-extern "C" hipError_t cvttmi_launch_downsample_filtered_layered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst,
-                                                                size_t dstPitch, size_t dstLayer, uint32_t srcW, uint32_t srcH,
-                                                                uint32_t layers, int kind, uint32_t filter, hipStream_t stream)
+extern "C" hipError_t cvttmi_launch_downsample_filtered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
+                                                        size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind,
+                                                        uint32_t filter, hipStream_t stream)
 {
     if (layers == 0 || layers > kMipMaxLayers)
         return hipErrorInvalidValue;
-    return filteredByKind<true>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, filter, stream);
+    return filteredByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, filter, stream);
 }

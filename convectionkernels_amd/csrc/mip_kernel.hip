@@ -43,18 +43,15 @@ __device__ __forceinline__ uint32_t boxWord(uint32_t a, uint32_t b, uint32_t c, 
 }
 
 // One output texel per lane.  Texel = uint32_t (RGBA8) or uint2 (RGBA16F).
-// LAYERED (here and in the wide kernel): workgroup z takes layer z of a texture array, `srcLayer` / `dstLayer` bytes further on.
-template <int KIND, bool LAYERED>
+// Here and in the wide kernel workgroup z takes layer z of a texture array, `srcLayer` / `dstLayer` bytes further on (one image: z = 0).
+template <int KIND>
 __global__ void __launch_bounds__(256) cvttmi_downsample_narrow_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                         uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW,
                                                                         uint32_t srcH, uint32_t dstW, uint32_t dstH, size_t srcLayer,
                                                                         size_t dstLayer)
 {
-    if (LAYERED)
-    {
-        src += blockIdx.z * srcLayer;
-        dst += blockIdx.z * dstLayer;
-    }
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= dstW)
         return;
@@ -82,16 +79,13 @@ __global__ void __launch_bounds__(256) cvttmi_downsample_narrow_kernel(const uin
 // 16 bytes of output per lane: chunk `i` of a row is output bytes [16 i, 16 i + 16) from input bytes [32 i, 32 i + 32) of
 // rows 2y and 2y + 1.  chunks = dstW * texel bytes / 16, exact; the input rows hold at least 2 * dstW texels, so no clamp
 // in x, and the launcher sends srcH == 1 to the narrow kernel, so none in y.
-template <int KIND, bool LAYERED>
+template <int KIND>
 __global__ void __launch_bounds__(256) cvttmi_downsample_wide_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                       uint8_t *__restrict__ dst, size_t dstPitch, uint32_t chunks,
                                                                       uint32_t dstH, size_t srcLayer, size_t dstLayer)
 {
-    if (LAYERED)
-    {
-        src += blockIdx.z * srcLayer;
-        dst += blockIdx.z * dstLayer;
-    }
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= chunks)
         return;
@@ -121,50 +115,42 @@ __global__ void __launch_bounds__(256) cvttmi_downsample_wide_kernel(const uint8
     }
 }
 
-// layers == 0: one image (the instances without LAYERED, as before texture arrays existed); otherwise `layers` (at most the z
-// limit of a grid: the caller cuts longer arrays) images `srcLayer` / `dstLayer` bytes apart, one launch for all of them
-template <int KIND, bool LAYERED>
+// `layers` (at most the z limit of a grid: the caller cuts longer arrays) images `srcLayer` / `dstLayer` bytes apart, one launch
+// for all of them
+template <int KIND>
 hipError_t launchDownsample(const MipLayers &m, hipStream_t stream)
 {
     const MipLaunch L = mipLaunchShape(m, KIND == kRGBA16F ? 8u : 4u);
     if (L.wide)
-        hipLaunchKernelGGL((cvttmi_downsample_wide_kernel<KIND, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
+        hipLaunchKernelGGL((cvttmi_downsample_wide_kernel<KIND>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
                            (uint8_t *)m.dst, m.dstPitch, L.perRow, L.dstH, m.srcLayer, m.dstLayer);
     else
-        hipLaunchKernelGGL((cvttmi_downsample_narrow_kernel<KIND, LAYERED>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
+        hipLaunchKernelGGL((cvttmi_downsample_narrow_kernel<KIND>), L.grid, L.block, 0, stream, (const uint8_t *)m.src, m.srcPitch,
                            (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, L.dstW, L.dstH, m.srcLayer, m.dstLayer);
     return hipGetLastError();
 }
 
-template <bool LAYERED>
 hipError_t downsampleByKind(const MipLayers &m, int kind, hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
     switch (kind)
     {
-    case kRGBA8: return launchDownsample<kRGBA8, LAYERED>(m, stream);
-    case kRGBA16F: return launchDownsample<kRGBA16F, LAYERED>(m, stream);
-    case kRGBA8Snorm: return launchDownsample<kRGBA8Snorm, LAYERED>(m, stream);
+    case kRGBA8: return launchDownsample<kRGBA8>(m, stream);
+    case kRGBA16F: return launchDownsample<kRGBA16F>(m, stream);
+    case kRGBA8Snorm: return launchDownsample<kRGBA8Snorm>(m, stream);
     default: return hipErrorInvalidValue;
     }
 }
 } // namespace
 
-// srcW x srcH texels at d_src (srcPitch bytes between rows) -> max(1, srcW >> 1) x max(1, srcH >> 1) texels at d_dst.
+// srcW x srcH texels at d_src (srcPitch bytes between rows) -> max(1, srcW >> 1) x max(1, srcH >> 1) texels at d_dst, of `layers`
+// images (1 .. 65535) at once: layer z reads d_src + z * srcLayer and writes d_dst + z * dstLayer.
 // kind: CVTTMI_PIXELS_RGBA8 / _RGBA16F / _RGBA8_SNORM; pointers and pitches are multiples of the texel size (the caller checks).
-extern "C" hipError_t cvttmi_launch_downsample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW,
-                                               uint32_t srcH, int kind, hipStream_t stream)
-{
-    return downsampleByKind<false>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, 0, 0, 0}, kind, stream);
-}
-
-// ... of `layers` images (1 .. 65535) at once: layer z reads d_src + z * srcLayer and writes d_dst + z * dstLayer
-extern "C" hipError_t cvttmi_launch_downsample_layered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
-                                                       size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind,
-                                                       hipStream_t stream)
+extern "C" hipError_t cvttmi_launch_downsample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
+                                               size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, hipStream_t stream)
 {
     if (layers == 0 || layers > kMipMaxLayers)
         return hipErrorInvalidValue;
-    return downsampleByKind<true>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, stream);
+    return downsampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, stream);
 }

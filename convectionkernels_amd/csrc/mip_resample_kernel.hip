@@ -123,7 +123,7 @@ __device__ __forceinline__ uint32_t plainByte(int s) // s: the second pass's sum
     return static_cast<uint32_t>(min(max(t, 0), (256 << 18) - 1)) >> 18;
 }
 
-template <int KIND, int RULE, int NTAPS, bool LAYERED>
+template <int KIND, int RULE, int NTAPS>
 __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                   uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
                                                                   uint32_t dstW, uint32_t dstH, size_t srcLayer, size_t dstLayer,
@@ -138,11 +138,8 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
     __shared__ Entry hbuf[kRows * kTileX];
     __shared__ short4 pbuf[RULE == kNormal ? kRows * kTileX : 1]; // NORMAL: the plain h' of channels 0..2
     __shared__ SrgbTables tables;                                 // (no LDS is allocated where it is not read)
-    if (LAYERED)
-    {
-        src += blockIdx.z * srcLayer;
-        dst += blockIdx.z * dstLayer;
-    }
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
     if (RULE == kSrgb)
     {
         loadSrgbTables(tables);
@@ -304,7 +301,7 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
     }
 }
 
-template <int KIND, int RULE, int NTAPS, bool LAYERED>
+template <int KIND, int RULE, int NTAPS>
 hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps, hipStream_t stream)
 {
     const uint32_t dstW = m.srcW > 1u ? m.srcW >> 1 : 1u, dstH = m.srcH > 1u ? m.srcH >> 1 : 1u;
@@ -315,26 +312,25 @@ hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps
         bits |= m.srcLayer;
     const uint32_t wide = (bits & 15u) == 0 ? 1u : 0u;
     const uint32_t tilesY = (dstH + kTileY - 1u) / kTileY;
-    const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers ? m.layers : 1u);
-    hipLaunchKernelGGL((cvttmi_mipresample_kernel<KIND, RULE, NTAPS, LAYERED>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
+    const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers);
+    hipLaunchKernelGGL((cvttmi_mipresample_kernel<KIND, RULE, NTAPS>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
                        (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, taps);
     return hipGetLastError();
 }
 
-template <int KIND, int RULE, bool LAYERED>
+template <int KIND, int RULE>
 hipError_t resampleByTaps(const MipLayers &m, uint32_t wrap, const MipTaps &taps, uint32_t count, hipStream_t stream)
 {
     switch (count)
     {
-    case 4: return launchResample<KIND, RULE, 4, LAYERED>(m, wrap, taps, stream);
-    case 8: return launchResample<KIND, RULE, 8, LAYERED>(m, wrap, taps, stream);
-    case 12: return launchResample<KIND, RULE, 12, LAYERED>(m, wrap, taps, stream);
+    case 4: return launchResample<KIND, RULE, 4>(m, wrap, taps, stream);
+    case 8: return launchResample<KIND, RULE, 8>(m, wrap, taps, stream);
+    case 12: return launchResample<KIND, RULE, 12>(m, wrap, taps, stream);
     default: return hipErrorInvalidValue;
     }
 }
 
 // RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL; anything else is hipErrorInvalidValue
-template <bool LAYERED>
 hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
@@ -345,34 +341,26 @@ hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t 
     for (uint32_t k = 0; k < 12u; k++)
         t.w[k] = k < count ? taps[k] : 0;
     if (kind == kRGBA8 && rule == kPlain)
-        return resampleByTaps<kRGBA8, kPlain, LAYERED>(m, wrap, t, count, stream);
+        return resampleByTaps<kRGBA8, kPlain>(m, wrap, t, count, stream);
     if (kind == kRGBA8 && rule == kSrgb)
-        return resampleByTaps<kRGBA8, kSrgb, LAYERED>(m, wrap, t, count, stream);
+        return resampleByTaps<kRGBA8, kSrgb>(m, wrap, t, count, stream);
     if (kind == kRGBA8 && rule == kNormal)
-        return resampleByTaps<kRGBA8, kNormal, LAYERED>(m, wrap, t, count, stream);
+        return resampleByTaps<kRGBA8, kNormal>(m, wrap, t, count, stream);
     if (kind == kRGBA8Snorm && rule == kPlain)
-        return resampleByTaps<kRGBA8Snorm, kPlain, LAYERED>(m, wrap, t, count, stream);
+        return resampleByTaps<kRGBA8Snorm, kPlain>(m, wrap, t, count, stream);
     if (kind == kRGBA8Snorm && rule == kNormal)
-        return resampleByTaps<kRGBA8Snorm, kNormal, LAYERED>(m, wrap, t, count, stream);
+        return resampleByTaps<kRGBA8Snorm, kNormal>(m, wrap, t, count, stream);
     return hipErrorInvalidValue;
 }
 } // namespace
 
-// One level under a mip kernel: `rule` = CVTTMI_MIP_FILTER_BOX (the plain rule), _SRGB or _NORMAL, `wrap` = 0 or one
-// CVTTMI_MIP_WRAP_* flag, taps[0 .. count - 1] the kernel's Q14 table (count = 4, 8 or 12)
-extern "C" hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch, void *d_dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
-                                             int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
-{
-    return resampleByKind<false>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, 0, 0, 0}, kind, rule, wrap, taps, count, stream);
-}
-
-// ... and the same level of `layers` images, the layer in the grid's z
-extern "C" hipError_t cvttmi_launch_resample_layered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
-                                                     size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule,
-                                                     uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
+// One level of `layers` images (1 .. 65535, the layer in the grid's z) under a mip kernel: `rule` = CVTTMI_MIP_FILTER_BOX (the plain
+// rule), _SRGB or _NORMAL, `wrap` = 0 or one CVTTMI_MIP_WRAP_* flag, taps[0 .. count - 1] the kernel's Q14 table (count = 4, 8 or 12)
+extern "C" hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch, size_t dstLayer,
+                                             uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule, uint32_t wrap,
+                                             const int16_t *taps, uint32_t count, hipStream_t stream)
 {
     if (layers == 0 || layers > kMipMaxLayers)
         return hipErrorInvalidValue;
-    return resampleByKind<true>(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, taps, count,
-                                stream);
+    return resampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, taps, count, stream);
 }

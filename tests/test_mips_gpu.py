@@ -254,6 +254,33 @@ def test_rejections(gpu_ctx):
         gpu_ctx.build_mips(src[: w * h * 4].view(h, w, 4), levels=7)
 
 
+def test_python_calls_reject_what_the_single_image_route_rejected(gpu_ctx):
+    """encode_mips takes its averaging rule from the format: an int8 image goes with bc4s / bc5s alone.  With bc7 it always was a
+    CvttError; with the other formats it used to be averaged as int8, which the one-layer texture call cannot do, so it is
+    refused, never averaged as uint8.  Rows that overlap or are no whole texels apart are refused, not copied."""
+    import torch
+    signed = torch.from_numpy(_image(37, 10, SNORM).copy()).cuda()
+    for fmt in ("bc7", "bc1", "bc3", "bc4u", "bc5u", "etc2", "etc2rgba", "bc6hu"):
+        with pytest.raises(api.CvttError):
+            gpu_ctx.encode_mips(fmt, signed)
+    got = gpu_ctx.encode_mips("bc4s", signed)
+    want = gpu_ctx.encode_mips("bc4s", signed.view(torch.uint8))  # (the same bytes under the format's rule)
+    assert len(got) == 6 and all((a.cpu().numpy() == b.cpu().numpy()).all() for a, b in zip(got, want))
+    with pytest.raises(api.CvttError):
+        gpu_ctx.encode_mips("nothing", torch.zeros((4, 4, 3), dtype=torch.uint8, device="cuda"))  # (format first, as before)
+    image = torch.from_numpy(_image(37, 10, RGBA8).copy()).cuda()
+    overlapping = torch.as_strided(image, (10, 37, 4), (36 * 4, 4, 1))
+    odd = torch.as_strided(torch.zeros(4096, dtype=torch.uint8, device="cuda"), (10, 37, 4), (37 * 4 + 2, 4, 1))
+    for bad in (overlapping, odd, image[:1].expand(10, 37, 4)):
+        with pytest.raises(api.CvttError):
+            gpu_ctx.build_mips(bad)
+        with pytest.raises(api.CvttError):
+            gpu_ctx.encode_mips("bc1", bad)
+    # a wider pitch is taken in place
+    window = torch.zeros((10, 40, 4), dtype=torch.uint8, device="cuda")[:, 2:39]
+    assert gpu_ctx.build_mips(window)[0].data_ptr() == window.data_ptr()
+
+
 @pytest.mark.parametrize("fmt,flag,read_mips,read_one", [("bc1", ["-dds"], container.read_dds_mips, container.read_dds),
                                                          ("etc2", [], container.read_ktx_mips, container.read_ktx)])
 def test_packer_writes_the_chain(gpu_ctx, tmp_path, capsys, fmt, flag, read_mips, read_one):

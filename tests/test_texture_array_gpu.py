@@ -1,7 +1,9 @@
-"""Texture arrays and cube maps on the GPU: Context.encode_texture against encode_mips of every layer, the C entry in guarded
-buffers, cvttmi_build_mips_array_device against build_mips of every layer, what the entries reject, and packer / unpacker end to
-end.  The shapes are a few hundred blocks: (3, 37x21) has padding tiles to drop, odd sizes and levels narrower than a group down
-to 1x1; (6, 32x32) is the cube without padding; (2, 260x9) has more than 64 tiles a row, so a wave crosses block rows and levels,
+"""Texture arrays and cube maps on the GPU: Context.encode_texture against encode_image of every level image the numpy restatement
+(tests/mip_filter_ref.py) makes of every layer, the C entry in guarded buffers, cvttmi_build_mips_array_device against the
+restatement's level images of every layer, what the entries reject, and packer / unpacker end to end.  (A single image is a texture
+of one layer through the same code, so encode_mips / build_mips per layer are no independent reference.)
+The shapes are a few hundred blocks: (3, 37x21) has padding tiles to drop, odd sizes and levels narrower than a group down to
+1x1; (6, 32x32) is the cube without padding; (2, 260x9) has more than 64 tiles a row, so a wave crosses block rows and levels,
 and its height reaches 1 long before its width; (2, 1x1) is one level of one block; (1, 70x5)."""
 import ctypes
 import functools
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 import guarded
+import mip_filter_ref
 from convectionkernels_amd import api, container, packer, unpacker
 
 pytestmark = pytest.mark.gpu
@@ -43,15 +46,22 @@ def _images(fmt, layers, w, h):
     return res
 
 
+def _ref_chain(image, filt, levels=None):
+    """the restatement's level images of one layer, in the layer's dtype (the restatement reads halfs as uint16 bit patterns)"""
+    bits = image.view(np.uint16) if image.dtype == np.float16 else image
+    return [level.view(image.dtype) for level in mip_filter_ref.chain(bits, filt, levels)]
+
+
 @functools.lru_cache(maxsize=None)
 def _reference(fmt, layers, w, h, levels=None, mip_filter="box"):
-    """[layer][level] numpy blocks of encode_mips of every layer: computed once, shared, read-only"""
+    """[layer][level] numpy blocks: encode_image of every level image the restatement makes of every layer (what
+    test_mips_gpu.py holds encode_mips to): computed once, shared, read-only"""
     import torch
     ctx = api.default_context()
     res = []
     for image in _images(fmt, layers, w, h):
-        chain = ctx.encode_mips(fmt, torch.from_numpy(image.copy()).cuda(), levels=levels, mip_filter=mip_filter)
-        res.append([t.cpu().numpy() for t in chain])
+        chain = _ref_chain(image, mip_filter, levels)
+        res.append([ctx.encode_image(fmt, torch.from_numpy(level.copy()).cuda()).cpu().numpy() for level in chain])
     for chain in res:
         for a in chain:
             a.setflags(write=False)
@@ -228,7 +238,10 @@ def test_build_mips_array_equals_build_mips_of_every_layer(gpu_ctx, filt, kind, 
     import torch
     host = _kind_images(kind, layers, w, h)
     ctx = _ctx()
-    want = [[t.cpu().numpy() for t in ctx.build_mips(torch.from_numpy(i.copy()).cuda(), signed=kind == SNORM, filter=filt)] for i in host]
+    want = [_ref_chain(i, filt) for i in host]
+    for i, ref in zip(host, want):  # (build_mips of a layer: the same bytes, as the name says)
+        single = ctx.build_mips(torch.from_numpy(i.copy()).cuda(), signed=kind == SNORM, filter=filt)
+        assert len(single) == len(ref) and all((a.cpu().numpy().view(np.uint8) == b.view(np.uint8)).all() for a, b in zip(single, ref))
     images = torch.from_numpy(host.copy()).cuda()
     got = ctx.build_mips_array(images, signed=kind == SNORM, filter=filt)
     assert len(got) == layers
@@ -275,6 +288,17 @@ def test_layers_off_a_16_byte_boundary(gpu_ctx, filt):
     for chain, ref in zip(got, want):
         for a, b in zip(chain, ref):
             assert (a.cpu().numpy() == b).all()
+    # ONE layer with that layer pitch: the strides of a single layer say nothing about its rows, so the launch is the one the
+    # single-image entry makes of the same image; same bytes, into a pyramid of one layer
+    one = api.texture_layout(w, h, 4, 16, len(layout), 1)
+    view, check = guarded.device_buffer(one.pyramidBytes, poison=POISON, what="pyramid of one layer")
+    assert _build_array_c(ctx, view.data_ptr(), one.pyramidBytes, src.data_ptr(), w, h, row_pitch, layer_pitch, RGBA8, len(layout), 1, filt) == 0
+    single, check_single = guarded.device_buffer(one.pyramidBytes, poison=POISON, what="pyramid of the single-image entry")
+    assert api.load_library().cvttmi_build_mips_filtered_device(ctx._h, single.data_ptr(), one.pyramidBytes, src.data_ptr(), w, h, row_pitch, RGBA8,
+                                                                len(layout), filt, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+    check_single(_expected_pyramids(want[:1], layout, one))
+    check(check_single.payload())
+    unchanged()
 
 
 # ---- 4. rejections ----
