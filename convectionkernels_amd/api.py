@@ -368,6 +368,17 @@ TEXTURE_FORMATS = {
     "bc5s": (11, 16, 64, 0x3), "etc1": (12, 8, 64, 0x7), "etc2punchthrough": (13, 8, 64, 0xF), "eac": (14, 8, 64, 0x8),
     "r11u": (15, 8, 32, 0x1), "r11s": (16, 8, 32, 0x1),
 }
+# What a texel of a format is (csrc/texture_formats.h, CvttTexelClass): "unorm8" unless named here.  "half": float16 RGB, no
+# PSNR; "snorm8": int8; "r11": an int16 scalar, the one class without an image form.
+_TEXEL_CLASS = {"bc6hu": "half", "bc6hs": "half", "bc4s": "snorm8", "bc5s": "snorm8", "r11u": "r11", "r11s": "r11"}
+
+
+def texel_class(fmt):
+    return _TEXEL_CLASS.get(fmt, "unorm8")
+
+
+def has_image_form(fmt):
+    return fmt in TEXTURE_FORMATS and texel_class(fmt) != "r11"
 
 
 # pixel kinds (include/cvtt_mi355x.h CVTTMI_PIXELS_*); the SNORM kind exists for the mip filter alone
@@ -569,7 +580,7 @@ class ErrorReport:
         self.totals = totals
         self.channel_mask = int(totals.channelMask)
         self.texels = int(totals.texels)
-        hdr = fmt in ("bc6hu", "bc6hs")
+        hdr = texel_class(fmt) == "half"
         self.sse = [float(totals.sseHdr[c]) if hdr else int(totals.sse[c]) for c in range(4)]
         self.mse = [(s / self.texels if self.texels else float("nan")) if (self.channel_mask >> c) & 1 else 0.0
                     for c, s in enumerate(self.sse)]
@@ -876,11 +887,11 @@ class Context:
     @staticmethod
     def _decoded_layout(fmt, n):
         """(shape, numpy dtype) of the decoded blocks: what the format's encoder reads"""
-        if fmt in ("bc6hu", "bc6hs"):
+        if texel_class(fmt) == "half":
             return (n, 16, 4), np.int16
-        if fmt in ("r11u", "r11s"):
+        if texel_class(fmt) == "r11":
             return (n, 16), np.int16
-        return (n, 16, 4), (np.int8 if fmt in ("bc4s", "bc5s") else np.uint8)
+        return (n, 16, 4), (np.int8 if texel_class(fmt) == "snorm8" else np.uint8)
 
     def decode(self, fmt, packed, stream=None):
         """(N, bytes) packed blocks of `fmt` (numpy or CUDA tensor) -> the layout its encoder reads: (N,16,4) uint8
@@ -915,7 +926,7 @@ class Context:
         device.  numpy inputs go through the host entry, CUDA tensors through the device entry on `stream`.
         per_block: also return each block's summed squared error (uint32; float32 for BC6H) as ErrorReport.per_block."""
         fid, bpb, tex, _ = self._texture_format(fmt)
-        hdr = fmt in ("bc6hu", "bc6hs")
+        hdr = texel_class(fmt) == "half"
         if isinstance(packed, np.ndarray):
             b = np.ascontiguousarray(packed, np.uint8)
             s = np.ascontiguousarray(blocks)
@@ -943,7 +954,7 @@ class Context:
 
     def _measure_device(self, fmt, n, per_block, stream, device, call):
         import torch
-        hdr = fmt in ("bc6hu", "bc6hs")
+        hdr = texel_class(fmt) == "half"
         # (per-block values are uint32 below 2^31 -- at most 16 x 2047^2 -- so an int32 tensor holds them; the totals need no
         # initial value: the call writes all of them, on `stream`)
         tot = torch.empty(ctypes.sizeof(ErrorTotals), dtype=torch.uint8, device=device)
@@ -1017,7 +1028,7 @@ class Context:
         "bc6hu", "bc6hs" from an (H,W,4) half-float image."""
         h, w = int(image.shape[0]), int(image.shape[1])
         blocks = self.tile_image(image, stream)
-        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
+        if not has_image_form(fmt):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
         packed = self.encode(fmt, blocks, options, plan, stream=stream)
         return packed if w % 32 == 0 else self.compact_rows(packed, w, h, stream)
@@ -1071,9 +1082,9 @@ class Context:
         times the blocks' size), so that kernels on a caller's own stream never outlive it: any level kept keeps all of it.
         Copy (clone) the levels to keep for long."""
         import torch
-        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
+        if not has_image_form(fmt):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
-        if isinstance(image, torch.Tensor) and image.dtype == torch.int8 and fmt not in ("bc4s", "bc5s"):
+        if isinstance(image, torch.Tensor) and image.dtype == torch.int8 and texel_class(fmt) != "snorm8":
             raise CvttError("%s is not encoded from an int8 image (bc4s / bc5s are)" % fmt)
         return self.encode_texture(fmt, self._one_layer(image), options, plan, levels, "layer", mip_filter, stream, kernel, wrap)[0]
 
@@ -1138,13 +1149,13 @@ class Context:
         encode_mips.  The allocation behind .base also holds the call's work space (texture_layout's workBytes, several times the
         blocks), so any view kept keeps that too: clone what is kept for long."""
         import torch
-        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 reads PixelBlockScalarS16: no image form)
+        if not has_image_form(fmt):  # (R11 reads PixelBlockScalarS16: no image form)
             raise CvttError("unknown format %r" % (fmt,))
         fid, bpb, _, _ = TEXTURE_FORMATS[fmt]
         images, row_pitch, layer_pitch = self._images_in(images)
         n, h, w = (int(v) for v in images.shape[:3])
         esz = images.element_size()
-        if (esz == 2) != (fmt in ("bc6hu", "bc6hs")):
+        if (esz == 2) != (texel_class(fmt) == "half"):
             raise CvttError("%s is encoded from %s images" % (fmt, "RGBA16F" if esz == 1 else "RGBA8"))
         options = options if options is not None else Options()
         if fmt == "bc7" and plan is None:
@@ -1177,10 +1188,10 @@ class Context:
     def _image_dtype(fmt):
         """torch dtype of the (H, W, 4) image `fmt` decodes into"""
         import torch
-        return torch.float16 if fmt in ("bc6hu", "bc6hs") else torch.int8 if fmt in ("bc4s", "bc5s") else torch.uint8
+        return torch.float16 if texel_class(fmt) == "half" else torch.int8 if texel_class(fmt) == "snorm8" else torch.uint8
 
     def _image_format(self, fmt, what):
-        if fmt not in TEXTURE_FORMATS or fmt in ("r11u", "r11s"):  # (R11 decodes to PixelBlockScalarS16: no image form)
+        if not has_image_form(fmt):  # (R11 decodes to PixelBlockScalarS16: no image form)
             raise CvttError("%s: %r has no image form" % (what, fmt) if fmt in TEXTURE_FORMATS else "unknown format %r" % (fmt,))
         return TEXTURE_FORMATS[fmt][:2]
 

@@ -33,6 +33,24 @@ def test_decode_matches_reference_goldens(gpu_ctx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("fmt,key", [("bc7", "bc7"), ("bc6hu", "bc6u"), ("bc6hs", "bc6s")])
+def test_decode_kernel_edges(gpu_ctx, fmt, key):
+    """The block-decode kernel at the edges of its 256-lane workgroups, host and device entry, every block against the
+    reference's output: 8 blocks (the smallest count: one partly filled workgroup), 264 = 256 + 8 (across one workgroup
+    boundary into a nearly empty one), and the whole fixture (2 624 / 2 304 / 2 112 blocks: every mode, the reserved ids; a
+    last workgroup of 64 lanes for bc7 and bc6hs, nine full workgroups for bc6hu)"""
+    import torch
+    g = np.load(os.path.join(GOLD, "decode.npz"))
+    packed, exp = g[key + "_in"], g[key + "_out"]
+    assert len(packed) == {"bc7": 2624, "bc6hu": 2304, "bc6hs": 2112}[fmt]
+    for n in (8, 264, len(packed)):
+        host = gpu_ctx.decode(fmt, packed[:n])
+        assert host.shape == exp[:n].shape and (host == exp[:n]).all(), (fmt, n)
+        dev = gpu_ctx.decode(fmt, torch.from_numpy(packed[:n]).cuda()).cpu().numpy()
+        assert dev.shape == exp[:n].shape and (dev == exp[:n]).all(), (fmt, n)
+
+
+@pytest.mark.gpu
 def test_decode_vs_reference_on_this_box(gpu_ctx, ref_lib):
     rng = np.random.Generator(np.random.PCG64(99))
     rnd = rng.integers(0, 256, (4096, 16), dtype=np.uint8)

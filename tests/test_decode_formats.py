@@ -211,14 +211,29 @@ def test_decoders_match_restatement(gpu_ctx, fmt):
 
 @pytest.mark.gpu
 def test_decode_bc7_bc6h_unchanged(gpu_ctx):
+    """decode("bc7") / decode_bc7 and decode("bc6h*") / decode_bc6h are two spellings of one C entry: each is held to the
+    reference's own output (tests/golden/decode.npz), not to the other; on random bytes they still agree"""
     g = np.load(os.path.join(GOLD, "decode.npz"))
     rnd = random_blocks("bc7")
-    for packed in (g["bc7_in"], rnd):
-        assert (gpu_ctx.decode("bc7", packed) == gpu_ctx.decode_bc7(packed)).all()
-    for fmt, key in (("bc6hu", "bc6u_in"), ("bc6hs", "bc6s_in")):
-        for packed in (g[key], rnd):
-            assert (gpu_ctx.decode(fmt, packed) == gpu_ctx.decode_bc6h(packed, signed=(fmt == "bc6hs"))).all()
-    assert (gpu_ctx.decode("bc7", g["bc7_in"]) == g["bc7_out"]).all()
+    for fmt, key, named in _BC67_SPELLINGS:
+        for spelling in (lambda p: gpu_ctx.decode(fmt, p), lambda p: named(gpu_ctx, p)):
+            assert (spelling(g[key + "_in"]) == g[key + "_out"]).all(), fmt
+        assert (gpu_ctx.decode(fmt, rnd) == named(gpu_ctx, rnd)).all(), fmt
+
+
+_BC67_SPELLINGS = (("bc7", "bc7", lambda ctx, p: ctx.decode_bc7(p)),
+                   ("bc6hu", "bc6u", lambda ctx, p: ctx.decode_bc6h(p, signed=False)),
+                   ("bc6hs", "bc6s", lambda ctx, p: ctx.decode_bc6h(p, signed=True)))
+
+
+@pytest.mark.gpu
+def test_decode_bc7_bc6h_spellings_vs_reference_on_this_box(gpu_ctx, ref_lib):
+    """random bytes (every mode, reserved ids): both spellings against the reference's decoders, as tests/test_decode.py"""
+    rnd = random_blocks("bc7")
+    exp = {"bc7": ref_lib.decode_bc7(rnd), "bc6hu": ref_lib.decode_bc6h(rnd, False), "bc6hs": ref_lib.decode_bc6h(rnd, True)}
+    for fmt, _, named in _BC67_SPELLINGS:
+        assert (gpu_ctx.decode(fmt, rnd) == exp[fmt]).all(), fmt
+        assert (named(gpu_ctx, rnd) == exp[fmt]).all(), fmt
 
 
 def _measure_cases():

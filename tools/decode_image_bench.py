@@ -12,6 +12,9 @@
    The outputs of the new call and of the parent's route are compared as well.
 2. A 13-level 4096^2 chain for bc1 and bc7 (Context.encode_mips of the noise image): cvttmi_decode_mips_device, one launch,
    against one cvttmi_decode_image_device per level into the same buffers.
+3. --block-decode: nothing of the above, only cvttmi_decode_device (the decode inside "parent", without the untiling) on 2^20
+   random blocks of bc7, bc6hu and bc6hs, every sample kept: one process measures one build of the library (CVTTMI_LIB), so an
+   A/B of two builds alternates processes (profiles/decode/one_kernel_bench.json).
 Every figure is the median of the repetitions with the minimum and the 10th / 90th percentile beside it.  --small shrinks
 every size by 16 (a rehearsal of the script, not a measurement).  Prints one JSON line per case and writes them all to --out
 with the library's source SHA-256."""
@@ -128,10 +131,32 @@ def chain_case(torch, api, ctx, fmt, size, reps):
     return rec
 
 
+def block_decode_case(torch, api, ctx, fmt, n, reps, warmup=5):
+    """cvttmi_decode_device alone (what Context.decode calls, the "parent_route" above without its untiling): n random blocks
+    -> decoded blocks, device events around each call; every sample is kept"""
+    fid, bpb, tex, _ = api.TEXTURE_FORMATS[fmt]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(fid)
+    packed = torch.randint(0, 256, (n, bpb), dtype=torch.uint8, device="cuda", generator=g)
+    out = torch.empty(n * tex, dtype=torch.uint8, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def decode():
+        rc = ctx._lib.cvttmi_decode_device(ctx._h, fid, out.data_ptr(), packed.data_ptr(), n, stream)
+        assert rc == 0, rc
+
+    us = alternate(torch, {"decode": decode}, reps, warmup)["decode"]
+    rec = {"case": "block_decode", "format": fmt, "blocks": n, "samples_us": [round(t, 2) for t in us]}
+    rec.update(stats(us))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--block-decode", action="store_true",
+                    help="only the block decode of bc7 / bc6hu / bc6hs at 2^20 blocks (the library: CVTTMI_LIB, for an A/B of two builds)")
     ap.add_argument("--out", default=os.path.join("profiles", "decode_image", "decode_image_bench.json"))
     args = ap.parse_args()
     import torch
@@ -139,6 +164,15 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("decode_image_bench needs an MI355X: nothing is measured without one")
     ctx = api.Context(0)
+    if args.block_decode:
+        results = [block_decode_case(torch, api, ctx, fmt, (1 << 20) // (256 if args.small else 1), args.reps) for fmt in ("bc7", "bc6hu", "bc6hs")]
+        for rec in results:
+            print(json.dumps({k: v for k, v in rec.items() if k != "samples_us"}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"library_source_sha256": api.library_source_sha256(), "device": torch.cuda.get_device_name(0),
+                       "small": bool(args.small), "results": results}, f, indent=1)
+        return
     # the HIP runtime this process already has mapped (one runtime per process: api.load_library)
     hip = ctypes.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line))
     hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]

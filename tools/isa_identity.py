@@ -55,6 +55,11 @@ def instructions(path):
                     text = m.group(1) + "<distance>"
                     MASKED[0] += 1
                 cur.append(text)
+    # the zero bytes that align the next function are disassembled with the one before them ("..." for a run of them, a single
+    # zero dword as the instruction it encodes); how many there are depends on the neighbours, not on the kernel
+    for ins in res.values():
+        while ins and ins[-1] in ("...", "v_cndmask_b32_e32 v0, s0, v0, vcc"):
+            ins.pop()
     return res
 
 
