@@ -60,8 +60,16 @@ struct ShapeBest
 {
     float err;
     u32 ep0, ep1; // packed RGBA endpoints
-    u32 idxLo, idxHi; // 4 bits per pixel, by pixel position
+    u32 idxLo, idxHi; // 4 bits per pixel: compact by member (evalChain), or by dualIndexSlot (evalDual)
 };
+
+// The index sets of a dual-plane candidate (ShapeBest::idxLo / idxHi out of evalDual, WorkState::idxLo .. idx2Hi, s_parked)
+// keep the layout the pixel loop of the search produces them in: idxLo holds pixels 0..7, idxHi pixels 8..15, and pixel p
+// sits in the 4-bit slot dualIndexSlot(p) of its word -- byte k of a word holds pixel k of the even group of four in its low
+// nibble and pixel k of the odd group in its high nibble, which is one v_lshl_or_b32 per pair of groups from the bytes that
+// v_cvt_pk_u8_f32 files.  Pixel 0 stays in slot 0.  packDualPlane reads every pixel from its slot: the sets are sorted to
+// their pixels once per block, where the bits are written, instead of in every round that improves a plane.
+__device__ __forceinline__ constexpr int dualIndexSlot(int p) { return 2 * (p & 3) + ((p >> 2) & 1); }
 
 __device__ __forceinline__ u32 packEP(const int (&e)[4])
 {
@@ -507,8 +515,8 @@ struct WorkState
     int partOrIS; // partition, or index selector for modes 4/5 (union in the reference, BC67.cpp:67-75)
     int rotation;
     u32 ep[3][2];
-    u32 idxLo, idxHi;   // primary indexes, 4 bits per pixel
-    u32 idx2Lo, idx2Hi; // secondary indexes (modes 4/5)
+    u32 idxLo, idxHi;   // primary indexes, 4 bits per pixel (modes 4/5: in the slots of dualIndexSlot, else by pixel position)
+    u32 idx2Lo, idx2Hi; // secondary indexes (modes 4/5, in the slots of dualIndexSlot)
 };
 
 // Fix-ups + bit packing of a mode 4 / mode 5 block (reference BC67.cpp:2003-2203) by one lane: with the mode a template
@@ -581,13 +589,14 @@ __device__ __forceinline__ void packDualPlane(const WorkState &work, u32 &w0, u3
     put((e0 >> 24) >> (8 - alphaBits), alphaBase);
     put((e1 >> 24) >> (8 - alphaBits), alphaBase + alphaBits);
     constexpr int idxBase = alphaBase + 2 * alphaBits;
+    // (the index sets arrive in the search's layout: pixel px in slot dualIndexSlot(px), a constant shift like any other)
 #pragma unroll
     for (int px = 0; px < 16; px++)
-        put(((px < 8 ? iLo : iHi) >> (4 * (px & 7))) & 0xfu, idxBase + 2 * px - (px > 0 ? 1 : 0));
+        put(((px < 8 ? iLo : iHi) >> (4 * dualIndexSlot(px))) & 0xfu, idxBase + 2 * px - (px > 0 ? 1 : 0));
     constexpr int idx2Base = idxBase + 31;
 #pragma unroll
     for (int px = 0; px < 16; px++)
-        put(((px < 8 ? jLo : jHi) >> (4 * (px & 7))) & 0xfu, idx2Base + alphaIndexBits * px - (px > 0 ? 1 : 0));
+        put(((px < 8 ? jLo : jHi) >> (4 * dualIndexSlot(px))) & 0xfu, idx2Base + alphaIndexBits * px - (px > 0 ? 1 : 0));
     w0 = (u32)lo;
     w1 = (u32)(lo >> 32);
     w2 = (u32)hi;

@@ -46,11 +46,12 @@ __device__ __forceinline__ void levelTable(int e0, int e1, bool threeBit, u32 &t
     }
 }
 
-// four byte-wide indexes -> four nibbles in the low 16 bits
-__device__ __forceinline__ u32 nibblesOf(u32 b4)
+// One group of four pixels (16 bytes) of the block's copy in LDS, at the byte address `addr` of the LDS segment.
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 ldsQuad(u32 addr)
 {
-    const u32 t = b4 | (b4 >> 4);
-    return __builtin_amdgcn_perm(0u, t, 0x0c0c0200u);
+    const u32x4 v = *(const __attribute__((address_space(3))) u32x4 *)(size_t)addr;
+    return make_uint4(v.x, v.y, v.z, v.w);
 }
 
 // One (mode, rotation, index selector) configuration of the dual-plane modes 4/5 (reference BC67.cpp:1725-1940): sub-lane
@@ -176,20 +177,22 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
             float slowRGB = 0.0f, slowA = 0.0f;               // slow indexing: the error of the chosen candidates
             v2f tv01 = {0.0f, 0.0f}, tv23 = {0.0f, 0.0f};
             v2f tt2 = {0.0f, 0.0f}, ts2 = {0.0f, 0.0f}; // {RGB plane, alpha plane}
-            u32 rgbLo = 0, rgbHi = 0, aLo = 0, aHi = 0; // 4 bits per pixel
+            u32 rgbLo = 0, rgbHi = 0, aLo = 0, aHi = 0; // 4 bits per pixel, pixel p in slot dualIndexSlot(p)
 
             // an address the optimiser cannot see through: the loads stay inside the round (hoisted, they would hold 16
-            // registers again, and the 64 conversions with them)
-            const u32 *sPr = sP;
+            // registers again, and the 64 conversions with them).  What is hidden is the 32-bit LDS address, not a generic
+            // pointer, so the loads stay ds_read_b128: no 64-bit address pair, no vmcnt wait, no trip down the vector-memory path
+            u32 sPr = (u32)(size_t)(const __attribute__((address_space(3))) u32 *)sP;
             asm volatile("" : "+v"(sPr));
             float errorRGB, errorA;
             if constexpr (FAST)
             {
+                u32 iRprev = 0, iAprev = 0; // the even group's index bytes, until the odd group's join them
 #pragma unroll
                 for (int g = 0; g < 4; g++)
                 {
                     u32 iR4 = 0, iA4 = 0;
-                    const uint4 L = *reinterpret_cast<const uint4 *>(sPr + 4 * g);
+                    const uint4 L = ldsQuad(sPr + 16u * (u32)g);
                     const u32 Pg[4] = {L.x, L.y, L.z, L.w};
 #pragma unroll
                     for (int k = 0; k < 4; k++)
@@ -200,13 +203,14 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                         dist = dist + p23.x;
                         // clampRound in two halves.  The last round's index goes to v_cvt_pk_u8_f32 alone, which rounds to nearest even
                         // and saturates at 0 itself: the upper clamp is all it needs (clampHigh, cvtt_kernel_common.h).  The other
-                        // rounds' index also weights the refiner and takes the rest: clampRound(v, hi) = rintf(fmaxf(clampHigh(v, hi), 0)).
+                        // rounds' index also weights the refiner and takes the rest: clampRound(v, hi) = rintf(fmaxf(clampHigh(v, hi), 0)),
+                        // the rounding first (roundClampLow: the same bits, one v_max_f32 less per index).
                         float fRGB = clampHigh(dist, rgbMax);
                         float fA = clampHigh(p23.y, alphaMaxV);
                         if (!last)
                         {
-                            fRGB = rintf(fmaxf(fRGB, 0.0f));
-                            fA = rintf(fmaxf(fA, 0.0f));
+                            fRGB = roundClampLow(fRGB);
+                            fA = roundClampLow(fA);
                         }
                         // the indexes are small integers: v_cvt_pk_u8_f32 converts and files one as byte k in one instruction
                         iR4 = __builtin_amdgcn_cvt_pk_u8_f32(fRGB, (u32)k, iR4);
@@ -225,15 +229,16 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                             ts2 = ts2 + t2;
                         }
                     }
-                    if (g < 2)
+                    // the bytes as they are, the odd group in the high nibbles (dualIndexSlot): every index is below 8
+                    if (g & 1)
                     {
-                        rgbLo |= nibblesOf(iR4) << (16 * g);
-                        aLo |= nibblesOf(iA4) << (16 * g);
+                        (g == 1 ? rgbLo : rgbHi) = iRprev | (iR4 << 4);
+                        (g == 1 ? aLo : aHi) = iAprev | (iA4 << 4);
                     }
                     else
                     {
-                        rgbHi |= nibblesOf(iR4) << (16 * (g - 2));
-                        aHi |= nibblesOf(iA4) << (16 * (g - 2));
+                        iRprev = iR4;
+                        iAprev = iA4;
                     }
 #pragma unroll
                     for (int ch = 0; ch < 4; ch++)
@@ -268,8 +273,8 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
 #pragma unroll 1
                 for (int g = 0; g < 4; g++)
                 {
-                    const uint4 L = *reinterpret_cast<const uint4 *>(sPr + 4 * g);
-                    u32 r4 = 0, a4 = 0; // the group's indexes, 4 bits per pixel
+                    const uint4 L = ldsQuad(sPr + 16u * (u32)g);
+                    u32 r4 = 0, a4 = 0; // the group's indexes, one per byte (the fast path's layout: dualIndexSlot)
 #pragma unroll
                     for (int k = 0; k < 4; k++)
                     {
@@ -350,18 +355,18 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                             tt2 = tt2 + t2 * t2;
                             ts2 = ts2 + t2;
                         }
-                        r4 |= (u32)iRGB << (4 * k);
-                        a4 |= (u32)iA << (4 * k);
+                        r4 |= (u32)iRGB << (8 * k);
+                        a4 |= (u32)iA << (8 * k);
                     }
                     if (g < 2)
                     {
-                        rgbLo |= r4 << (16 * g);
-                        aLo |= a4 << (16 * g);
+                        rgbLo |= r4 << (4 * g);
+                        aLo |= a4 << (4 * g);
                     }
                     else
                     {
-                        rgbHi |= r4 << (16 * (g - 2));
-                        aHi |= a4 << (16 * (g - 2));
+                        rgbHi |= r4 << (4 * (g - 2));
+                        aHi |= a4 << (4 * (g - 2));
                     }
                 }
                 errorRGB = slowRGB;

@@ -2132,7 +2132,8 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
             if (packed.mode < 4 || packed.mode == 7)
             {
                 // single-plane results carry their indexes compact, subset after subset in member order: sort them to their
-                // pixels (sub-lane c places pixels 4c .. 4c + 3; modes 4 / 5 are positional already, mode 6 is one subset of 16)
+                // pixels (sub-lane c places pixels 4c .. 4c + 3; mode 6 is one subset of 16; modes 4 / 5 keep the layout of their
+                // search, dualIndexSlot, which packDualPlane reads)
                 const int p = packed.partOrIS;
                 const bool three = (packed.mode == 0 || packed.mode == 2);
                 const u32 m1 = three ? (s_pm3[p] & 0xffffu) : (u32)s_pm2[p];

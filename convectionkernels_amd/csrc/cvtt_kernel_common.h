@@ -85,6 +85,16 @@ __device__ __forceinline__ float clampRound(float v, float hi)
 // tools/cvt_pk_u8_probe.hip checks the identity on all 2^32 bit patterns for hi = 3, 7, 15 on the device.
 __device__ __forceinline__ float clampHigh(float v, float hi) { return fminf(v, hi); }
 
+// The rest of clampRound for a value c that clampHigh produced, in the rounds whose index also weights the refiner:
+// rintf(fmaxf(c, 0.0f)), with the rounding first.  fmaxf in another basic block than the v_min_f32 (the wave-uniform
+// `if (!last)` of the dual-plane search stands between the two) makes the compiler canonicalise its operand, a
+// v_max_f32 c, c, c ahead of the v_max_f32 c, 0, c -- it no longer sees that c is the quieted result of a v_min_f32.  The
+// result of v_rndne_f32 in the same block needs none, and the order does not matter to the value: for c > 0 both forms round
+// the same number; for c <= 0 (-0, (-0.5, 0) and -inf included) both give +0, v_max_f32 ordering -0 below +0; c is never a NaN
+// (clampHigh).  tools/clamp_low_probe.hip compares the two forms, and the single v_max_f32 written in assembly, on all 2^32
+// patterns ahead of the upper clamp for hi = 3 and 7: the same 32 bits each.  (Not v_med3_f32, which maps a NaN to 0, not hi.)
+__device__ __forceinline__ float roundClampLow(float c) { return fmaxf(rintf(c), 0.0f); }
+
 // 1/n rounded toward zero for the pixel count n of a subset (entry 0, an empty subset: 0), as binary32 bit patterns: L * kRcpDown[n]
 // never exceeds L / n for L >= 0, which is what a lower bound needs (bc7_kernel.hip: subsetBound2D).  One constant per count
 // instead of a v_cvt + v_rcp_f32 (quarter rate, 1 ulp either way) per subset and partition.
