@@ -203,6 +203,7 @@ _EXPORTS = (
     "cvttmi_decode_image_device", "cvttmi_decode_mips_device",
     "cvttmi_build_mips_filtered_device", "cvttmi_srgb_tables", "cvttmi_mip_kernel_taps",
     "cvttmi_texture_layout", "cvttmi_texture_subresource", "cvttmi_build_mips_array_device", "cvttmi_encode_texture_device",
+    "cvttmi_resize_taps", "cvttmi_resize_work_bytes", "cvttmi_resize_launches", "cvttmi_resize_image_device",
 )
 
 _lib = None
@@ -302,6 +303,10 @@ def load_library():
     lib.cvttmi_texture_subresource.argtypes = [U, U, I, U, U, U, I, U, U, ctypes.POINTER(N), ctypes.POINTER(N)]
     lib.cvttmi_build_mips_array_device.argtypes = [P, P, N, P, U, U, N, N, I, U, U, U, P]
     lib.cvttmi_encode_texture_device.argtypes = [P, I, P, N, P, U, U, N, N, U, U, U, I, P, P, P, P, N, P]
+    lib.cvttmi_resize_taps.argtypes = [U, U, U, P, P, ctypes.POINTER(U)]
+    lib.cvttmi_resize_work_bytes.argtypes = [U, U, U, U, I, U, U, ctypes.POINTER(N)]
+    lib.cvttmi_resize_launches.argtypes = [U, U, U, U, I, U, ctypes.POINTER(U)]
+    lib.cvttmi_resize_image_device.argtypes = [P, P, U, U, N, N, P, U, U, N, N, I, U, U, P, N, P]
     lib.cvttmi_decode_bc7_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.cvttmi_decode_bc7.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     lib.cvttmi_decode_bc6h_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
@@ -426,6 +431,51 @@ def mip_kernel_taps(name):
     if rc != 0:
         raise CvttError("cvttmi_mip_kernel_taps failed (%d)" % rc)
     return taps[:count.value].copy()
+
+
+# resizing (include/cvtt_mi355x.h, "resize"): the mip kernels, and kernel code 0 = an area-average box
+RESIZE_KERNELS = dict(MIP_KERNELS, box=0)
+RESIZE_RULES = {"box": MIP_FILTER_BOX, "srgb": MIP_FILTER_SRGB, "normal": MIP_FILTER_NORMAL}
+
+
+def resize_filter_word(kernel="lanczos3", filter="box", wrap="clamp"):
+    """the `filter` value of the resize calls: rule (a name of RESIZE_RULES or its value) | kernel (a name of RESIZE_KERNELS) | wrap"""
+    if kernel not in RESIZE_KERNELS:
+        raise CvttError("unknown resize kernel %r (one of %s)" % (kernel, ", ".join(RESIZE_KERNELS)))
+    if wrap not in MIP_WRAPS:
+        raise CvttError("unknown wrap mode %r (one of %s)" % (wrap, ", ".join(MIP_WRAPS)))
+    if isinstance(filter, str) and filter not in RESIZE_RULES:
+        raise CvttError("unknown resize filter %r (one of %s)" % (filter, ", ".join(RESIZE_RULES)))
+    return mip_filter_value(filter) | RESIZE_KERNELS[kernel] | MIP_WRAPS[wrap]
+
+
+def resize_taps(src, dst, kernel, wrap="clamp"):
+    """cvttmi_resize_taps: the tables of one axis of `src` texels resized to `dst` under a kernel (a name of RESIZE_KERNELS) ->
+    (first, weights): first[x], int32, the unwrapped source coordinate of output x's tap 0; weights[x, k], int16 Q14, every row
+    summing to 16384.  `wrap` does not change the table: tap k reads first[x] + k wrapped by it."""
+    import numpy as np
+    lib, n = load_library(), ctypes.c_uint32(0)
+    word = resize_filter_word(kernel, "box", wrap)
+    src, dst = _u32(src, "src"), _u32(dst, "dst")
+    rc = lib.cvttmi_resize_taps(src, dst, word, None, None, ctypes.byref(n))
+    if rc != 0:
+        raise CvttError("cvttmi_resize_taps(%d -> %d) failed (%d): sizes are 1 .. 65535" % (src, dst, rc))
+    weights, first = np.zeros((dst, n.value), np.int16), np.zeros(dst, np.int32)
+    rc = lib.cvttmi_resize_taps(src, dst, word, weights.ctypes.data, first.ctypes.data, ctypes.byref(n))
+    if rc != 0:
+        raise CvttError("cvttmi_resize_taps(%d -> %d) failed (%d): the table does not keep the sums inside int32" % (src, dst, rc))
+    return first, weights
+
+
+def resize_launches(src_w, src_h, dst_w, dst_h, kernel="lanczos3", filter="box", signed=False):
+    """cvttmi_resize_launches: 1 where Context.resize of these sizes runs as one launch through LDS, 2 where it goes through an
+    intermediate in its work space"""
+    n = ctypes.c_uint32(0)
+    rc = load_library().cvttmi_resize_launches(_u32(src_w, "src_w"), _u32(src_h, "src_h"), _u32(dst_w, "dst_w"), _u32(dst_h, "dst_h"),
+                                               PIXELS_RGBA8_SNORM if signed else PIXELS_RGBA8, resize_filter_word(kernel, filter), ctypes.byref(n))
+    if rc != 0:
+        raise CvttError("cvttmi_resize_launches failed (%d)" % rc)
+    return n.value
 
 
 def srgb_tables():
@@ -1138,6 +1188,49 @@ class Context:
         per_level = [images.unbind(0)] + [typed.as_strided((n, L.height, L.width, 4), (sizes.pyramidLayerBytes // esz, 4 * L.width, 4, 1),
                                                            L.byteOffset // esz).unbind(0) for L in layout[1:]]
         return [[views[l] for views in per_level] for l in range(n)]
+
+    # -- resize: any size to any size on the device (cvtt_mi355x.h, "resize") --
+    def resize(self, images, width, height, kernel="lanczos3", filter="box", wrap="clamp", signed=False, out=None, stream=None):
+        """(H, W, 4) or (L, H, W, 4) CUDA tensor, uint8 or int8 -> the same rank resized to `width` x `height`
+        (cvttmi_resize_image_device: all layers in one call).  kernel: "box" (area average), "triangle", "mitchell", "lanczos3" or
+        "kaiser"; going down it is stretched by the ratio, going up it is not.  filter: "box" (the plain rule), "srgb" (colour in
+        linear light, uint8 only) or "normal" (renormalised) -- build_mips's names without the "+alpha" ones; wrap: "clamp",
+        "repeat" or "mirror".  int8, or signed=True: the bytes are read as int8.  At exactly half the size the result is
+        build_mips(kernel=kernel)[1].  out: a CUDA tensor of the result's shape and dtype to write into (its rows and layers may be
+        strided, its texels not)."""
+        import torch
+        single = isinstance(images, torch.Tensor) and images.dim() == 3
+        images, row_pitch, layer_pitch = self._images_in(self._one_layer(images) if single else images)
+        if images.element_size() != 1:
+            raise CvttError("resize takes RGBA8 images (uint8 or int8)")
+        n, h, w = (int(v) for v in images.shape[:3])
+        width, height = _u32(width, "width"), _u32(height, "height")
+        kind = PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+        word = resize_filter_word(kernel, filter, wrap)
+        shape = (n, height, width, 4)
+        if out is None:
+            result = torch.empty(shape, dtype=images.dtype, device=images.device)
+        else:
+            result = out[None] if (isinstance(out, torch.Tensor) and out.dim() == 3) else out
+            if not (isinstance(result, torch.Tensor) and result.is_cuda and result.device == images.device and tuple(result.shape) == shape
+                    and result.dtype == images.dtype):
+                raise CvttError("out must be a CUDA tensor on %s of shape %s and dtype %s" % (images.device, shape[1:] if single else shape, images.dtype))
+            kept, out_row, out_layer = self._images_in(result)
+            if kept is not result:
+                raise CvttError("out must have contiguous texels, rows at least a row apart and layers at least an image apart")
+        if out is None:
+            out_row, out_layer = 4 * width, 4 * width * height
+        need = ctypes.c_size_t(0)
+        rc = self._lib.cvttmi_resize_work_bytes(w, h, width, height, kind, word, n, ctypes.byref(need))
+        if rc != 0:
+            raise CvttError("resize %dx%d -> %dx%d refused: sizes and layers are 1 .. 65535; uint8 images take box, srgb and normal, int8 images box and normal" % (w, h, width, height))
+        work = torch.empty(max(need.value, 1), dtype=torch.uint8, device=images.device)
+        self._check(self._lib.cvttmi_resize_image_device(self._h, result.data_ptr(), width, height, out_row, out_layer, images.data_ptr(), w, h,
+                                                         row_pitch, layer_pitch, kind, n, word, work.data_ptr(), need.value,
+                                                         ctypes.c_void_p(self._stream(stream, images.device))), "resize")
+        if stream is not None:  # the work space is read on the caller's stream: the allocator must not hand it out before that
+            work.record_stream(torch.cuda.ExternalStream(stream, device=images.device))
+        return out if out is not None else (result[0] if single else result)
 
     def encode_texture(self, fmt, images, options=None, plan=None, levels=None, order="layer", mip_filter="box", stream=None, kernel=None,
                        wrap="clamp"):

@@ -1,0 +1,421 @@
+// Resize to any size (include/cvtt_mi355x.h, "resize"): the Q14 two-pass rule of the mip kernels with one weight row per output
+// column and per output row.  RGBA8 and RGBA8_SNORM texels; the plain rule, SRGB and NORMAL; clamp, repeat and mirror.  The tables
+// (cvttmi_resize_taps: weights and first taps of both axes) lie in device memory, in the caller's work space:
+//   wx[k * dstW + x]  the weight of tap k of output column x (tap-major: the lanes of a wave read neighbouring columns)
+//   fx[x]             the unwrapped source column of its tap 0
+//   wy[y * ny + k], fy[y]  the same for output row y (row-major: a wave works on one row, the weight is the same for all its lanes)
+// The two passes, the layer in the grid's z:
+//   horizontal  entry (x, r), r a SOURCE row: h' of output column x from the nx taps of row r.  A lane walks its taps through
+//               the wrap with 4-byte reads; neighbouring lanes read overlapping texels (L1 / L2).
+//   vertical    output texel (x, y) from the ny entries (x, fy[y] + k), the row wrapped; one 4-byte store.
+// An entry is: plain int16 x 4; SRGB int32 x 4 (channel 3 the plain h'); NORMAL int16 x 4 of X and alpha plus int16 x 4 of the
+// plain bytes, which the vertical pass reads only where the three sums of X are all zero.
+// One launch where the footprint allows it (cvttmi_resize_fused_rows): a workgroup of 256 lanes owns a tile of kTileX x kTileY
+// output texels and keeps the entries of the source rows under it, fy[y0] .. fy[y1] + ny - 1, in LDS sized per launch (at most
+// kFusedLdsBytes with the sRGB tables).  Two launches otherwise, a workgroup on 256 columns of kRows neighbouring rows and the
+// entries of the whole image (dstW x srcH per layer) in the work space: nothing there depends on the ratio, a footprint of any
+// length is a loop.  The sRGB tables are copied to LDS once per workgroup (5.5 KB vertical, 0.5 KB horizontal).  No scratch.
+// Every product is a 24-bit multiply: |tap| <= 16385 + what a row is missing, a value or an h' below 2^17 (sRGB: T <= 65535,
+// |h'| <= (65535 P + 8192) >> 14 < 2^17 for the P < 2^15 that cvttmi_resize_taps lets through), and that function has checked that
+// the sums stay inside int32.
+#include "mip_common.h"
+#include <type_traits>
+
+#define CVTT_SRGB_TABLE __device__ const __attribute__((aligned(16))) // (the byte table is copied a word at a time)
+#include "srgb_tables.h"
+
+namespace
+{
+enum
+{
+    kPlain = 0,
+    kSrgb = 1,
+    kNormal = 2,
+    kWrapRepeat = 0x200,
+    kWrapMirror = 0x400,
+    kRows = 8,  // two launches: rows of one workgroup
+    kTileX = 64, // one launch: the tile of output texels of a workgroup
+    kTileY = 16,
+    kFusedLdsBytes = 52 * 1024 // ... and the LDS it may take: three workgroups share a CU's 160 KB
+};
+
+struct SrgbTables
+{
+    uint32_t next[256]; // [c] = U[c + 1], the threshold above code c; [255] = no sum reaches it
+    uint8_t coarse[4096];
+};
+
+struct NormalEntry
+{
+    short4 n, p; // h' of X (channels 0..2) and of alpha; h' of the plain bytes of channels 0..2
+};
+
+template <int RULE>
+struct EntryOf
+{
+    typedef typename std::conditional<RULE == kSrgb, int4, typename std::conditional<RULE == kNormal, NormalEntry, short4>::type>::type type;
+};
+
+__device__ __forceinline__ uint32_t srgbEncode(const SrgbTables &t, uint32_t S) // S <= 4 * 65535
+{
+    const uint32_t c = t.coarse[S >> 6];
+    return c + (S >= t.next[c] ? 1u : 0u);
+}
+
+// A coordinate that walks along a wrapped axis of n texels (the walk of mip_resample_kernel.hip): `pos` is the coordinate itself
+// (clamp), its place in the period n (repeat) or in the period 2 n of there-and-back (mirror).  One division where the walk starts.
+struct Walk
+{
+    int64_t pos;
+    uint32_t n, wrap;
+};
+
+__device__ __forceinline__ Walk walkFrom(int64_t i, uint32_t n, uint32_t wrap)
+{
+    Walk k = {i, n, wrap};
+    if (wrap != 0 && (i < 0 || i >= (int64_t)n))
+    {
+        const uint64_t p = wrap == kWrapMirror ? 2ull * n : (uint64_t)n;
+        k.pos = i >= 0 ? (int64_t)((uint64_t)i % p) : (int64_t)(p - 1u - ((uint64_t)(-i - 1) % p));
+    }
+    return k;
+}
+
+__device__ __forceinline__ uint32_t walkIndex(const Walk &k)
+{
+    if (k.wrap == kWrapMirror)
+        return static_cast<uint32_t>(k.pos < (int64_t)k.n ? k.pos : 2 * (int64_t)k.n - 1 - k.pos);
+    if (k.wrap == kWrapRepeat)
+        return static_cast<uint32_t>(k.pos);
+    return static_cast<uint32_t>(k.pos < 0 ? 0 : k.pos >= (int64_t)k.n ? (int64_t)k.n - 1 : k.pos);
+}
+
+__device__ __forceinline__ void walkStep(Walk &k)
+{
+    k.pos++;
+    if (k.wrap != 0 && k.pos == (k.wrap == kWrapMirror ? 2 * (int64_t)k.n : (int64_t)k.n))
+        k.pos = 0;
+}
+
+// the last step of the plain rule, clamp((s + 2^17) >> 18), as the clamp of the sum followed by the shift (mip_resample_kernel.hip
+// says why: shift-then-clamp of neighbouring channels becomes a packed instruction whose upper half came out wrong)
+template <int KIND>
+__device__ __forceinline__ uint32_t plainByte(int s)
+{
+    const int t = s + (1 << 17);
+    if (KIND == kRGBA8Snorm)
+        return static_cast<uint32_t>(min(max(t, -(128 << 18)), (128 << 18) - 1) >> 18) & 255u;
+    return static_cast<uint32_t>(min(max(t, 0), (256 << 18) - 1)) >> 18;
+}
+
+struct ResizeArgs
+{
+    const uint8_t *src;
+    uint8_t *dst;
+    void *mid; // two launches: the intermediate, dstW x srcH entries per layer, layers consecutive
+    size_t srcPitch, srcLayer, dstPitch, dstLayer;
+    uint32_t srcW, srcH, dstW, dstH;
+    const int16_t *wx, *wy;
+    const int32_t *fx, *fy;
+    uint32_t nx, ny, wrap;
+};
+
+__device__ __forceinline__ void loadLinear(uint16_t *lin) // 256 lanes
+{
+    lin[threadIdx.x] = k_srgbToLinear[threadIdx.x];
+}
+
+__device__ __forceinline__ void loadEncode(SrgbTables &t) // 256 lanes
+{
+    t.next[threadIdx.x] = threadIdx.x < 255u ? k_srgbThresholds[threadIdx.x] : 0xffffffffu;
+    for (uint32_t i = threadIdx.x; i < 1024u; i += 256u)
+        reinterpret_cast<uint32_t *>(t.coarse)[i] = reinterpret_cast<const uint32_t *>(k_srgbCoarse)[i];
+}
+
+// The horizontal pass of one entry: output column x of one source row.  tap: the column's weights, `stride` apart.
+template <int KIND, int RULE>
+__device__ __forceinline__ typename EntryOf<RULE>::type horizontalEntry(const ResizeArgs &a, const uint32_t *row, int32_t first, const int16_t *tap,
+                                                                        uint32_t stride, const uint16_t *lin)
+{
+    Walk w = walkFrom(first, a.srcW, a.wrap);
+    int h[7] = {0, 0, 0, 0, 0, 0, 0}; // 0..2: the colour channels under the rule; 3: alpha; 4..6 (NORMAL): the plain bytes of 0..2
+    for (uint32_t k = 0; k < a.nx; k++, tap += stride)
+    {
+        const uint32_t texel = row[walkIndex(w)];
+        walkStep(w);
+        const int q = *tap;
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            const uint32_t v = (texel >> (8 * c)) & 255u;
+            const int plain = KIND == kRGBA8Snorm ? static_cast<int>(static_cast<int8_t>(v)) : static_cast<int>(v);
+            int value = plain;
+            if (c < 3 && RULE == kSrgb)
+                value = lin[v];
+            if (c < 3 && RULE == kNormal)
+            {
+                value = KIND == kRGBA8Snorm ? max(plain, -127) : 2 * plain - 255;
+                h[4 + c] += __mul24(q, plain);
+            }
+            h[c] += __mul24(q, value);
+        }
+    }
+    const int h3 = (h[3] + 512) >> 10;
+    if constexpr (RULE == kSrgb)
+        return make_int4((h[0] + (1 << 13)) >> 14, (h[1] + (1 << 13)) >> 14, (h[2] + (1 << 13)) >> 14, h3);
+    else
+    {
+        const short4 e = make_short4((short)((h[0] + 512) >> 10), (short)((h[1] + 512) >> 10), (short)((h[2] + 512) >> 10), (short)h3);
+        if constexpr (RULE == kNormal)
+            return NormalEntry{e, make_short4((short)((h[4] + 512) >> 10), (short)((h[5] + 512) >> 10), (short)((h[6] + 512) >> 10), 0)};
+        else
+            return e;
+    }
+}
+
+// The vertical pass of one output texel: at(k) = the entry under tap k, tap[k] its weight.
+template <int KIND, int RULE, class At>
+__device__ __forceinline__ uint32_t verticalTexel(const int16_t *tap, uint32_t ny, const SrgbTables &tables, At at)
+{
+    int s[4] = {0, 0, 0, 0};
+    for (uint32_t k = 0; k < ny; k++)
+    {
+        const int q = tap[k];
+        short4 e16;
+        int4 e32;
+        if constexpr (RULE == kSrgb)
+            e32 = at(k);
+        else if constexpr (RULE == kNormal)
+            e16 = at(k).n;
+        else
+            e16 = at(k);
+        s[0] += __mul24(q, RULE == kSrgb ? e32.x : (int)e16.x);
+        s[1] += __mul24(q, RULE == kSrgb ? e32.y : (int)e16.y);
+        s[2] += __mul24(q, RULE == kSrgb ? e32.z : (int)e16.z);
+        s[3] += __mul24(q, RULE == kSrgb ? e32.w : (int)e16.w);
+    }
+    uint32_t out = plainByte<KIND>(s[3]) << 24;
+    if constexpr (RULE == kPlain)
+    {
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            out |= plainByte<KIND>(s[c]) << (8 * c);
+    }
+    else if constexpr (RULE == kSrgb)
+    {
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            out |= srgbEncode(tables, static_cast<uint32_t>(min(max((s[c] + (1 << 11)) >> 12, 0), 4 * 65535))) << (8 * c);
+    }
+    else
+    {
+        const int S[3] = {(s[0] + 128) >> 8, (s[1] + 128) >> 8, (s[2] + 128) >> 8};
+        if ((S[0] | S[1] | S[2]) == 0)
+        {
+            int p[3] = {0, 0, 0};
+            for (uint32_t k = 0; k < ny; k++)
+            {
+                const short4 e = at(k).p;
+                const int q = tap[k];
+                p[0] += __mul24(q, e.x);
+                p[1] += __mul24(q, e.y);
+                p[2] += __mul24(q, e.z);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                out |= plainByte<KIND>(p[c]) << (8 * c);
+        }
+        else
+        {
+            const float fx = static_cast<float>(S[0]), fy = static_cast<float>(S[1]), fz = static_cast<float>(S[2]);
+            const float f[3] = {fx, fy, fz};
+            const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+            {
+                const float q = f[c] / len;
+                const int r = KIND == kRGBA8Snorm ? min(max(static_cast<int>(floorf(q * 127.0f + 0.5f)), -127), 127)
+                                                  : min(max(static_cast<int>(floorf(q * 127.5f + 128.0f)), 0), 255);
+                out |= (static_cast<uint32_t>(r) & 255u) << (8 * c);
+            }
+        }
+    }
+    return out;
+}
+
+// ---- one launch: a tile of kTileX x kTileY output texels per workgroup, the two passes separated through LDS ----
+// The source rows under a tile are fy[y0] .. fy[y1] + ny - 1 (fy does not decrease); `rows` of them at most, over all tiles.
+template <int KIND, int RULE>
+__global__ void __launch_bounds__(256) cvttmi_resize_fused_kernel(ResizeArgs a, uint32_t rows)
+{
+    typedef typename EntryOf<RULE>::type Entry;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    Entry *hbuf = reinterpret_cast<Entry *>(lds); // rows x kTileX entries
+    __shared__ SrgbTables tables;                 // (no LDS is allocated where it is not read)
+    __shared__ uint16_t lin[RULE == kSrgb ? 256 : 1];
+    if constexpr (RULE == kSrgb)
+    {
+        loadLinear(lin);
+        loadEncode(tables);
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x, x = lane & (kTileX - 1), x0 = blockIdx.x * kTileX, y0 = blockIdx.y * kTileY;
+    const uint32_t tileH = min(a.dstH - y0, (uint32_t)kTileY);
+    const bool inside = x0 + x < a.dstW;
+    const int32_t top = a.fy[y0];
+    const uint32_t used = static_cast<uint32_t>(a.fy[y0 + tileH - 1] - top) + a.ny; // <= rows: the host has looked at every tile
+    if (inside && used <= rows)
+    {
+        const int32_t first = a.fx[x0 + x];
+        const int16_t *tap = a.wx + x0 + x;
+        Walk wy = walkFrom((int64_t)top + (lane / kTileX), a.srcH, a.wrap);
+        for (uint32_t r = lane / kTileX; r < used; r += 256u / kTileX)
+        {
+            const uint32_t *row = reinterpret_cast<const uint32_t *>(a.src + blockIdx.z * a.srcLayer + (size_t)walkIndex(wy) * a.srcPitch);
+            hbuf[r * kTileX + x] = horizontalEntry<KIND, RULE>(a, row, first, tap, a.dstW, lin);
+#pragma unroll
+            for (uint32_t i = 0; i < 256u / kTileX; i++)
+                walkStep(wy);
+        }
+    }
+    __syncthreads();
+    if (inside && used <= rows)
+    {
+        const uint32_t yg = lane / kTileX;
+        for (uint32_t j = 0; j < (uint32_t)kTileY / (256u / kTileX); j++)
+        {
+            const uint32_t y = y0 + yg * (kTileY / (256u / kTileX)) + j;
+            if (y >= y0 + tileH)
+                break;
+            const Entry *column = hbuf + static_cast<uint32_t>(a.fy[y] - top) * kTileX + x;
+            const uint32_t out = verticalTexel<KIND, RULE>(a.wy + (size_t)y * a.ny, a.ny, tables, [&](uint32_t k) { return column[k * kTileX]; });
+            reinterpret_cast<uint32_t *>(a.dst + blockIdx.z * a.dstLayer + (size_t)y * a.dstPitch)[x0 + x] = out;
+        }
+    }
+}
+
+// ---- two launches: any footprint ----
+template <int KIND, int RULE>
+__global__ void __launch_bounds__(256) cvttmi_resize_h_kernel(ResizeArgs a)
+{
+    typedef typename EntryOf<RULE>::type Entry;
+    __shared__ uint16_t lin[RULE == kSrgb ? 256 : 1];
+    if constexpr (RULE == kSrgb)
+    {
+        loadLinear(lin);
+        __syncthreads();
+    }
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.dstW)
+        return;
+    const int32_t first = a.fx[x];
+    const uint32_t r0 = blockIdx.y * kRows, r1 = min(r0 + kRows, a.srcH);
+    Entry *mid = static_cast<Entry *>(a.mid) + ((size_t)blockIdx.z * a.srcH + r0) * a.dstW + x;
+    for (uint32_t r = r0; r < r1; r++, mid += a.dstW)
+    {
+        const uint32_t *row = reinterpret_cast<const uint32_t *>(a.src + blockIdx.z * a.srcLayer + (size_t)r * a.srcPitch);
+        *mid = horizontalEntry<KIND, RULE>(a, row, first, a.wx + x, a.dstW, lin);
+    }
+}
+
+template <int KIND, int RULE>
+__global__ void __launch_bounds__(256) cvttmi_resize_v_kernel(ResizeArgs a)
+{
+    typedef typename EntryOf<RULE>::type Entry;
+    __shared__ SrgbTables tables; // (no LDS is allocated where it is not read)
+    if constexpr (RULE == kSrgb)
+    {
+        loadEncode(tables);
+        __syncthreads();
+    }
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.dstW)
+        return;
+    const Entry *mid = static_cast<const Entry *>(a.mid) + (size_t)blockIdx.z * a.srcH * a.dstW + x;
+    const uint32_t y0 = blockIdx.y * kRows, y1 = min(y0 + kRows, a.dstH);
+    for (uint32_t y = y0; y < y1; y++)
+    {
+        const int32_t first = a.fy[y];
+        // (the walk starts anew for the second loop of a NORMAL texel whose sums are zero: k counts up from 0 both times)
+        Walk w = walkFrom(first, a.srcH, a.wrap);
+        const uint32_t out = verticalTexel<KIND, RULE>(a.wy + (size_t)y * a.ny, a.ny, tables, [&](uint32_t k) {
+            if (k == 0)
+                w = walkFrom(first, a.srcH, a.wrap);
+            const Entry e = mid[(size_t)walkIndex(w) * a.dstW];
+            walkStep(w);
+            return e;
+        });
+        reinterpret_cast<uint32_t *>(a.dst + blockIdx.z * a.dstLayer + (size_t)y * a.dstPitch)[x] = out;
+    }
+}
+
+template <int KIND, int RULE>
+hipError_t launchResize(const ResizeArgs &a, uint32_t layers, uint32_t fusedRows, hipStream_t stream)
+{
+    if (fusedRows)
+    {
+        const dim3 grid((a.dstW + kTileX - 1u) / kTileX, (a.dstH + kTileY - 1u) / kTileY, layers);
+        hipLaunchKernelGGL((cvttmi_resize_fused_kernel<KIND, RULE>), grid, dim3(256), (size_t)fusedRows * kTileX * sizeof(typename EntryOf<RULE>::type),
+                           stream, a, fusedRows);
+        return hipGetLastError();
+    }
+    const uint32_t gx = (a.dstW + 255u) / 256u;
+    hipLaunchKernelGGL((cvttmi_resize_h_kernel<KIND, RULE>), dim3(gx, (a.srcH + kRows - 1u) / kRows, layers), dim3(256), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((cvttmi_resize_v_kernel<KIND, RULE>), dim3(gx, (a.dstH + kRows - 1u) / kRows, layers), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+} // namespace
+
+// bytes of one entry of the intermediate under a rule (0: no such rule)
+extern "C" size_t cvttmi_resize_entry_bytes(uint32_t rule)
+{
+    return rule == kPlain ? sizeof(EntryOf<kPlain>::type) : rule == kSrgb ? sizeof(EntryOf<kSrgb>::type) : rule == kNormal ? sizeof(EntryOf<kNormal>::type) : 0;
+}
+
+// The path of a resize, from the first taps of its dstH output rows (ny taps each): the most source rows under one tile where
+// they fit in kFusedLdsBytes of LDS next to the sRGB tables -- one launch --, else 0 -- two launches.  Host only.
+extern "C" uint32_t cvttmi_resize_fused_rows(uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny)
+{
+    const size_t entry = cvttmi_resize_entry_bytes(rule);
+    const size_t room = kFusedLdsBytes - (rule == kSrgb ? sizeof(SrgbTables) + 512u : 0u);
+    uint64_t rows = 0;
+    for (uint32_t y0 = 0; y0 < dstH; y0 += kTileY)
+    {
+        const uint32_t y1 = dstH - y0 < (uint32_t)kTileY ? dstH - 1u : y0 + kTileY - 1u;
+        const uint64_t used = (uint64_t)((int64_t)first[y1] - first[y0]) + ny;
+        rows = used > rows ? used : rows;
+    }
+    return entry && rows * kTileX * entry <= room ? static_cast<uint32_t>(rows) : 0u;
+}
+
+// `layers` images (1 .. 65535, sizes 1 .. 65535) resized under `rule` = CVTTMI_MIP_FILTER_BOX (the plain rule), _SRGB or _NORMAL and
+// `wrap` = 0 or one CVTTMI_MIP_WRAP_* flag.  d_wx (tap-major), d_fx, d_wy (row-major), d_fy: the tables, in device memory.
+// fusedRows = cvttmi_resize_fused_rows of d_fy's values; where it is 0, d_mid holds layers x srcH x dstW entries of
+// cvttmi_resize_entry_bytes(rule), on a 16-byte boundary.
+extern "C" hipError_t cvttmi_launch_resize(const void *d_src, size_t srcPitch, size_t srcLayer, uint32_t srcW, uint32_t srcH, void *d_dst,
+                                           size_t dstPitch, size_t dstLayer, uint32_t dstW, uint32_t dstH, uint32_t layers, int kind,
+                                           uint32_t rule, uint32_t wrap, const int16_t *d_wx, const int32_t *d_fx, uint32_t nx,
+                                           const int16_t *d_wy, const int32_t *d_fy, uint32_t ny, void *d_mid, uint32_t fusedRows,
+                                           hipStream_t stream)
+{
+    if (layers == 0 || layers > kMipMaxLayers || srcW == 0 || srcH == 0 || dstW == 0 || dstH == 0 || (srcW | srcH | dstW | dstH) > 65535u || nx == 0 ||
+        ny == 0 || (wrap != 0 && wrap != kWrapRepeat && wrap != kWrapMirror) || !d_wx || !d_fx || !d_wy || !d_fy || (!fusedRows && !d_mid) ||
+        (size_t)fusedRows * kTileX * cvttmi_resize_entry_bytes(rule) > kFusedLdsBytes)
+        return hipErrorInvalidValue;
+    const ResizeArgs a = {static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_dst), d_mid, srcPitch, srcLayer, dstPitch, dstLayer,
+                          srcW, srcH, dstW, dstH, d_wx, d_wy, d_fx, d_fy, nx, ny, wrap};
+    if (kind == kRGBA8 && rule == kPlain)
+        return launchResize<kRGBA8, kPlain>(a, layers, fusedRows, stream);
+    if (kind == kRGBA8 && rule == kSrgb)
+        return launchResize<kRGBA8, kSrgb>(a, layers, fusedRows, stream);
+    if (kind == kRGBA8 && rule == kNormal)
+        return launchResize<kRGBA8, kNormal>(a, layers, fusedRows, stream);
+    if (kind == kRGBA8Snorm && rule == kPlain)
+        return launchResize<kRGBA8Snorm, kPlain>(a, layers, fusedRows, stream);
+    if (kind == kRGBA8Snorm && rule == kNormal)
+        return launchResize<kRGBA8Snorm, kNormal>(a, layers, fusedRows, stream);
+    return hipErrorInvalidValue;
+}

@@ -1,6 +1,6 @@
 """Image -> compressed texture file on the MI355X: the caller side of the hot path.
 
-    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-mipkernel triangle|mitchell|lanczos3|kaiser] [-wrap clamp|repeat|mirror] [-alphaweight] [-srgb] [-metrics] [-array | -cube] input [input ...] output
+    python -m convectionkernels_amd.packer [-format F] [-uniform] [-fakebt709] [-quality Q] [-dds] [-mips] [-mipfilter box|srgb|normal] [-mipkernel triangle|mitchell|lanczos3|kaiser] [-wrap clamp|repeat|mirror] [-alphaweight] [-srgb] [-metrics] [-array | -cube] [-resize WxH | -maxsize N | -pow2 nearest|up|down] [-resizekernel box|triangle|mitchell|lanczos3|kaiser] [-resizerule box|srgb|normal] [-resizewrap clamp|repeat|mirror] input [input ...] output
 
 The command line follows the reference's example packer (etc2packer.cpp:44-105: `-format etc1|etc2rgb|etc2rgba|etc2punchthrough|r11u|r11s`,
 `-fakebt709`, `-uniform` (which overrides it), input, output; default etc2rgb, KTX output) and adds the BC formats (bc1..bc5, bc7; `-dds` for a DX10 DDS
@@ -24,7 +24,14 @@ clamp|repeat|mirror: how the kernel's taps leave the image (repeat: a tiling tex
 order +X -X +Y -Y +Z -Z, or of a cube array (6 n inputs).  Either also takes a single .npy of shape (L, H, W, 4).  All layers
 must be of one size, a cube's faces square.  The layers go through one call (Context.encode_texture) and into one KTX (level-major)
 or, with -dds, DDS (layer-major) file that a loader binds as an array or a cube; combines with -mips, -mipfilter, -alphaweight,
--srgb and -quality.  With -metrics the lines above are printed for every layer under a `layer N` heading.  Not for R11."""
+-srgb and -quality.  With -metrics the lines above are printed for every layer under a `layer N` heading.  Not for R11.
+-resize WxH, -maxsize N, -pow2 nearest|up|down (one of them): the image -- every layer of -array / -cube in one call -- is resized on
+the device (Context.resize) before anything else; -mips, -metrics and the container header see the new size.  -maxsize: the larger
+side becomes at most N, the aspect kept, each side max(1, floor(side * N / larger + 0.5)); never enlarges.  -pow2: each side on its own
+to the next power of two up, down, or the nearer of the two (the larger one from the middle on).  -resizekernel (default lanczos3; box is
+an area average), -resizerule box|srgb|normal (default box: the plain rule) and -resizewrap (default clamp) say how, and go only with
+one of the three.  Sizes are 1 .. 65535.  Not for bc6hu / bc6hs."""
+import re
 import sys
 
 import numpy as np
@@ -148,6 +155,38 @@ def encode_file_texture(images, fmt, options=None, plan=None, ctx=None, mips=Fal
     return [[host[(t.data_ptr() - start) // per: (t.data_ptr() - start) // per + t.shape[0]] for t in levels] for levels in blocks]
 
 
+def resized_size(w, h, resize=None, maxsize=None, pow2=None):
+    """the size -resize (w, h) / -maxsize N / -pow2 nearest|up|down gives a w x h image"""
+    if resize is not None:
+        w, h = resize
+    elif maxsize is not None:
+        if maxsize < 1:
+            raise ValueError("-maxsize: sizes are 1 .. 65535")
+        larger = max(w, h)
+        if larger > maxsize:
+            w, h = (max(1, (side * maxsize * 2 + larger) // (2 * larger)) for side in (w, h))
+    elif pow2 is not None:
+        def power(side):
+            below = 1 << (side.bit_length() - 1)
+            if below == side or pow2 == "down":
+                return below
+            return 2 * below if pow2 == "up" or side - below >= 2 * below - side else below
+        w, h = power(w), power(h)
+    if not (1 <= w <= 65535 and 1 <= h <= 65535):
+        raise ValueError("resize to %dx%d: sizes are 1 .. 65535" % (w, h))
+    return w, h
+
+
+def resize_file(images, width, height, kernel="lanczos3", rule="box", wrap="clamp", signed=False, ctx=None):
+    """(H, W, 4) or (L, H, W, 4) uint8 numpy image(s) -> the same resized to width x height on the device (all layers in one call)"""
+    import torch
+    ctx = ctx or api.default_context()
+    out = ctx.resize(torch.from_numpy(np.ascontiguousarray(images)).cuda(ctx.device), width, height, kernel=kernel, filter=rule, wrap=wrap,
+                     signed=signed)
+    torch.cuda.synchronize(ctx.device)
+    return out.cpu().numpy()
+
+
 def print_metrics(report, out=None):
     out = out or sys.stdout
     for c, name in enumerate("RGBA"):
@@ -169,6 +208,7 @@ def main(argv=None):
     fmt, uniform, fake, quality, dds, metrics, mips, paths = "etc2rgb", False, False, None, False, False, False, []
     mip_filter, alpha_weight, srgb, array, cube = None, False, False, False, False
     mip_kernel, wrap = None, None
+    resize, maxsize, pow2, size_flags, resize_kernel, resize_rule, resize_wrap = None, None, None, 0, None, None, None
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -194,6 +234,27 @@ def main(argv=None):
             i += 1
         elif a == "-wrap" and i + 1 < len(argv) and argv[i + 1] in api.MIP_WRAPS:
             wrap = argv[i + 1]
+            i += 1
+        elif a == "-resize" and i + 1 < len(argv) and re.match(r"^[0-9]+x[0-9]+$", argv[i + 1]):
+            resize = tuple(int(v) for v in argv[i + 1].split("x"))
+            size_flags += 1
+            i += 1
+        elif a == "-maxsize" and i + 1 < len(argv) and argv[i + 1].isdigit():
+            maxsize = int(argv[i + 1])
+            size_flags += 1
+            i += 1
+        elif a == "-pow2" and i + 1 < len(argv) and argv[i + 1] in ("nearest", "up", "down"):
+            pow2 = argv[i + 1]
+            size_flags += 1
+            i += 1
+        elif a == "-resizekernel" and i + 1 < len(argv) and argv[i + 1] in api.RESIZE_KERNELS:
+            resize_kernel = argv[i + 1]
+            i += 1
+        elif a == "-resizerule" and i + 1 < len(argv) and argv[i + 1] in api.RESIZE_RULES:
+            resize_rule = argv[i + 1]
+            i += 1
+        elif a == "-resizewrap" and i + 1 < len(argv) and argv[i + 1] in api.MIP_WRAPS:
+            resize_wrap = argv[i + 1]
             i += 1
         elif a == "-alphaweight":
             alpha_weight = True
@@ -236,6 +297,15 @@ def main(argv=None):
             raise ValueError("-%s: %s has no image form" % ("cube" if cube else "array", fmt))
         if dds and (array or cube) and container.FORMATS[fmt][3] is None:
             raise ValueError("%s has no DXGI format; use KTX" % fmt)
+        if size_flags > 1:
+            raise ValueError("-resize, -maxsize, -pow2: one of them")
+        for flag, value in (("-resizekernel", resize_kernel), ("-resizerule", resize_rule), ("-resizewrap", resize_wrap)):
+            if value is not None and not size_flags:
+                raise ValueError("%s goes with -resize, -maxsize or -pow2" % flag)
+        if size_flags and fmt in ("bc6hu", "bc6hs"):
+            raise ValueError("-resize, -maxsize, -pow2: %s is encoded from half-float images, which are not resized" % fmt)
+        if resize_rule == "srgb" and fmt in ("bc4s", "bc5s"):
+            raise ValueError("-resizerule srgb: %s reads the image as int8, which takes box or normal" % fmt)
         if cube and len(paths) > 2 and (len(paths) - 1) % 6 != 0:
             raise ValueError("-cube takes the 6 faces of a cube (+X -X +Y -Y +Z -Z) or 6 n of a cube array, got %d inputs" % (len(paths) - 1))
         if array or cube:
@@ -244,9 +314,21 @@ def main(argv=None):
                 raise ValueError("-cube needs 6 n square faces, got %d of %dx%d" % (layers.shape[0], layers.shape[2], layers.shape[1]))
         else:
             image = load_rgba8(paths[0])
+        if size_flags:
+            loaded = layers if (array or cube) else image
+            target = resized_size(loaded.shape[-2], loaded.shape[-3], resize, maxsize, pow2)
+            if cube and target[0] != target[1]:
+                raise ValueError("-cube: resizing to %dx%d leaves no square faces" % target)
     except (ValueError, OSError) as e:
         sys.stderr.write("%s\n" % e)
         return 1
+    if size_flags and target != (loaded.shape[-2], loaded.shape[-3]):
+        loaded = resize_file(loaded, target[0], target[1], resize_kernel or "lanczos3", resize_rule or "box", resize_wrap or "clamp",
+                             signed=fmt in ("bc4s", "bc5s"))
+        if array or cube:
+            layers = loaded
+        else:
+            image = loaded
     how = dict(mip_filter=mip_filter, kernel=mip_kernel, wrap=wrap or "clamp")
     options = api.Options()
     if uniform:  # etc2packer.cpp:202-205

@@ -434,6 +434,63 @@ int cvttmi_build_mips_filtered_device(cvttmi_context *ctx, void *d_pyramid, size
 int cvttmi_srgb_tables(uint16_t toLinear[256], uint32_t thresholds[255]);
 int cvttmi_mip_kernel_taps(uint32_t filter, int16_t taps[12], uint32_t *count);
 
+/* ---- resize: any source size to any destination size, up or down (not part of the reference's API) ----
+ * The Q14 two-pass rule of the mip kernels above with one weight row per output column and one per output row, where the mip
+ * kernels have one table for every texel.  The `filter` word is theirs: rule | kernel | wrap, rule = CVTTMI_MIP_FILTER_BOX (the
+ * plain rule), _SRGB or _NORMAL, wrap = 0 (clamp) or one CVTTMI_MIP_WRAP_* flag.  Kernel: the four CVTTMI_MIP_KERNEL_* codes, R = 1,
+ * 2, 3, 3, with the weight functions K(t) above, and -- in the resize calls only -- kernel code 0 = an area-average box (R = 1/2).
+ * The rule of one axis, src texels resized to dst texels (both 1 .. 65535), big = max(src, dst); everything up to the weights is
+ * integer arithmetic.  Going down the kernel is stretched by big / dst, going up it is not.
+ *   taps per row    n = ceil(2R big / dst);  box: n = ceil(big / dst) + 1
+ *   first tap       L = (2x + 1) src - dst - 2R big;  first[x] = floor(L / (2 dst)) + 1;  box: first[x] = floor((L + dst) / (2 dst)).
+ *                   Tap k of output x reads source coordinate first[x] + k (may be negative or >= src), wrapped as above.
+ *   weights         t = (double)(2 dst (first[x] + k) - (2x + 1) src + dst) / (double)(2 big);  w_k = K(t) in double precision;
+ *                   W = the sum of the w_k, added in index order;  q_k = floor(16384 (w_k / W) + 0.5)
+ *   box weights     exact integers in units of 1 / (2 dst): o_k = the overlap of [2 dst j - dst, 2 dst j + dst), j = first[x] + k, with
+ *                   [(2x + 1) src - dst - big, (2x + 1) src - dst + big) (the overlaps sum to 2 big);
+ *                   q_k = (2 * 16384 o_k + 2 big) / (4 big), integer division
+ *   the row's sum   what is missing to 16384 goes to the taps that hold the row's largest q, divided equally among them (the
+ *                   quotient truncated towards zero); the lowest index of them takes what does not divide.
+ *   dst = src       every row is a single 16384 at the tap that reads x, the others 0: an image resized to its own size is itself.
+ *                   The formulas above give exactly that for every kernel but Mitchell, whose K(0) = 8/9 would blur the image.
+ * At dst = src / 2 the rows are the mip kernels' table and first[x] = 2x + 1 - 2R.
+ * Guard: with P the largest sum of positive taps over the rows of a table, the table is refused (CVTTMI_E_INVALID) unless
+ * 65535 P < 2^31 and ((65535 P + 8192) >> 14) (2P - 16384) < 2^31 -- the int32 sums of both passes under every rule (the largest
+ * P observed is 20 870, Lanczos3).
+ * Arithmetic: exactly that of the mip kernels -- horizontal then vertical, int32, arithmetic shifts, no intermediate clamp --
+ * with the weight row of the output column in the first pass and of the output row in the second:
+ *   plain rule, and always channel 3:  h' = (h + 512) >> 10;  out = clamp((s + 2^17) >> 18, 0..255 or -128..127)
+ *   CVTTMI_MIP_FILTER_SRGB and _NORMAL: word for word as stated above for kernels.
+ * RGBA8 takes the plain rule, SRGB and NORMAL; RGBA8_SNORM the plain rule and NORMAL; RGBA16F and ALPHA_WEIGHTED are refused for the
+ * reasons given above for kernels.
+ * cvttmi_resize_taps: host only, no context; the one owner of the rule (the device call uses its output).  Reports *tapsPerRow = n;
+ *   with weights != NULL it also fills weights[x * n + k] (dst x n values) and first[x] (dst values).  Only the kernel field of
+ *   `filter` matters to the table; the word must be a valid one.  CVTTMI_E_INVALID: a size of 0 or above 65535, a word that is
+ *   none, NULL tapsPerRow, weights without first, a table the guard refuses.
+ * cvttmi_resize_work_bytes: host only, no context.  *workBytes = what cvttmi_resize_image_device needs at d_work for these
+ *   arguments: the tables of both axes and, where the resize takes two launches, the intermediate (layers x srcH x dstW entries
+ *   of 8 bytes, 16 under SRGB and NORMAL).  cvttmi_resize_launches: *launches = 1 where the source rows under every tile of 64 x 16
+ *   output texels fit in LDS (52 KB), 2 otherwise.  Both reject (CVTTMI_E_INVALID) what the device call rejects
+ *   of these arguments.
+ * cvttmi_resize_image_device: `layers` images of srcW x srcH at d_src (srcRowPitchBytes between rows, srcLayerPitchBytes between
+ *   layers) -> dstW x dstH at d_dst, everything on hipStream, the layer in the grid's z.  d_work: caller memory on a 256-byte
+ *   boundary, at least workBytes = cvttmi_resize_work_bytes(..); its contents after the call are unspecified.  The tables are
+ *   built in page-locked memory of the context (a ring of four slots, each grown by the first call that needs more; a call with
+ *   the sizes and kernel of a slot's tables does not build them again) and copied to d_work on hipStream: calls queued back to
+ *   back wait for nothing but, after four later tables, the copy that read a slot.  Nothing else is allocated.  Writes exactly dstW x 4
+ *   bytes of each of the dstH rows of each layer -- not the pitch gaps -- and nothing outside d_work[0, workBytes).  Source and
+ *   destination must not overlap.  CVTTMI_E_INVALID with an error text before anything is queued, nothing written: NULL pointers, d_src
+ *   / d_dst not on a 4-byte, d_work not on a 256-byte boundary, a size or layers of 0 or above 65535, a row pitch below the row or no
+ *   multiple of 4, a layer pitch below height x row pitch or no multiple of 4, workBytes too small, a pixel kind other than RGBA8 /
+ *   RGBA8_SNORM, SRGB with RGBA8_SNORM, ALPHA_WEIGHTED or any other rule, an unknown kernel code, both wrap flags, a refused table. */
+int cvttmi_resize_taps(uint32_t src, uint32_t dst, uint32_t filter, int16_t *weights, int32_t *first, uint32_t *tapsPerRow);
+int cvttmi_resize_work_bytes(uint32_t srcW, uint32_t srcH, uint32_t dstW, uint32_t dstH, int pixelFormat, uint32_t filter, uint32_t layers,
+                             size_t *workBytes);
+int cvttmi_resize_launches(uint32_t srcW, uint32_t srcH, uint32_t dstW, uint32_t dstH, int pixelFormat, uint32_t filter, uint32_t *launches);
+int cvttmi_resize_image_device(cvttmi_context *ctx, void *d_dst, uint32_t dstW, uint32_t dstH, size_t dstRowPitchBytes, size_t dstLayerPitchBytes,
+                               const void *d_src, uint32_t srcW, uint32_t srcH, size_t srcRowPitchBytes, size_t srcLayerPitchBytes,
+                               int pixelFormat, uint32_t layers, uint32_t filter, void *d_work, size_t workBytes, void *hipStream);
+
 /* ---- texture arrays and cube maps (not part of the reference's API) ----
  * A texture is `layers` images of one size, each with `levels` mip levels; layers = array elements x faces.  A cube is 6 layers
  * in the order +X -X +Y -Y +Z -Z, a cube array 6 n layers.  Every layer has the chain of cvttmi_mip_layout; with T = that
