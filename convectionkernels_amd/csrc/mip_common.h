@@ -1,5 +1,5 @@
-// What the mip kernels share (mip_kernel.hip: the box filter; mip_filter_kernel.hip: the other filters): the pixel kinds, the
-// box rule on four bytes at once, and the shape of a level's launch.
+// What the mip and resize kernels share (mip_kernel.hip: the box filter; resample_common.h: every other filter): the pixel kinds,
+// the box rule on four bytes at once, and the shape of a level's launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +42,10 @@ struct MipLayers
     uint32_t layers;
 };
 const uint32_t kMipMaxLayers = 65535; // the z limit of a grid
+inline bool mipLayersOk(uint32_t layers)
+{
+    return layers != 0 && layers <= kMipMaxLayers;
+}
 
 // One level's launch.  The wide kernel (16 bytes of output per lane) runs when both row starts, both pitches and the output
 // width allow 16-byte accesses and no coordinate needs a clamp -- for every layer: the two layer strides enter the same test

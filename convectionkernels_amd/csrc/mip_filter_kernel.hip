@@ -7,56 +7,10 @@
 // The sRGB filters read their three tables from LDS (5.5 KB a workgroup, copied from constant memory by its 256 lanes): per
 // output texel twelve 16-bit reads of T and, per channel, one byte of C[S >> 6] = encode(S with its low six bits cleared) and one
 // threshold -- U's steps are above 64, so S passes at most one threshold more than its bucket's start.  No scratch.
-#include "mip_common.h"
-
-#define CVTT_SRGB_TABLE __device__ const __attribute__((aligned(16))) // (the byte table is copied a word at a time)
-#include "srgb_tables.h"
+#include "resample_common.h"
 
 namespace
 {
-enum
-{
-    kSrgb = 1,
-    kNormal = 2,
-    kAlphaWeighted = 0x100
-};
-
-struct SrgbTables
-{
-    uint32_t next[256]; // [c] = U[c + 1], the threshold above code c; [255] = no sum reaches it
-    uint16_t lin[256];
-    uint8_t coarse[4096];
-};
-
-// the workgroup's copy of the tables; every lane comes here, the ones without a texel too
-__device__ __forceinline__ void loadSrgbTables(SrgbTables &t)
-{
-    const uint32_t lanes = blockDim.x * blockDim.y, lane = threadIdx.y * blockDim.x + threadIdx.x;
-    for (uint32_t i = lane; i < 256u; i += lanes)
-    {
-        t.next[i] = i < 255u ? k_srgbThresholds[i] : 0xffffffffu;
-        t.lin[i] = k_srgbToLinear[i];
-    }
-    for (uint32_t i = lane; i < 1024u; i += lanes)
-        reinterpret_cast<uint32_t *>(t.coarse)[i] = reinterpret_cast<const uint32_t *>(k_srgbCoarse)[i];
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t srgbEncode(const SrgbTables &t, uint32_t S) // S <= 4 * 65535
-{
-    const uint32_t c = t.coarse[S >> 6];
-    return c + (S >= t.next[c] ? 1u : 0u);
-}
-
-template <int KIND>
-__device__ __forceinline__ int normalComponent(uint32_t texel, int ch)
-{
-    const uint32_t v = (texel >> (8 * ch)) & 255u;
-    if (KIND == kRGBA8Snorm)
-        return max(static_cast<int>(static_cast<int8_t>(v)), -127);
-    return 2 * static_cast<int>(v) - 255;
-}
-
 // one output texel from its four input texels (channel i = bits 8 i .. 8 i + 7)
 template <int KIND, int FILTER>
 __device__ __forceinline__ uint32_t filterTexel(const SrgbTables &t, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
@@ -67,7 +21,8 @@ __device__ __forceinline__ uint32_t filterTexel(const SrgbTables &t, uint32_t a,
         int s[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ch++)
-            s[ch] = normalComponent<KIND>(a, ch) + normalComponent<KIND>(b, ch) + normalComponent<KIND>(c, ch) + normalComponent<KIND>(d, ch);
+            s[ch] = ruleValue<KIND, kNormal>(a, ch, t.lin) + ruleValue<KIND, kNormal>(b, ch, t.lin) + ruleValue<KIND, kNormal>(c, ch, t.lin) +
+                    ruleValue<KIND, kNormal>(d, ch, t.lin);
         const uint32_t Q = static_cast<uint32_t>(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]); // <= 3 * 1020^2 < 2^24: exact as a float
         if (Q == 0)
             return box;
@@ -75,13 +30,7 @@ __device__ __forceinline__ uint32_t filterTexel(const SrgbTables &t, uint32_t a,
         uint32_t out = box & 0xff000000u;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++)
-        {
-            const float q = static_cast<float>(s[ch]) / len;
-            // (the product and the sum round separately: -ffp-contract=off)
-            const int r = KIND == kRGBA8Snorm ? min(max(static_cast<int>(floorf(q * 127.0f + 0.5f)), -127), 127)
-                                              : min(max(static_cast<int>(floorf(q * 127.5f + 128.0f)), 0), 255);
-            out |= (static_cast<uint32_t>(r) & 255u) << (8 * ch);
-        }
+            out |= normalByte<KIND>(static_cast<float>(s[ch]) / len) << (8 * ch);
         return out;
     }
     const bool srgb = (FILTER & kSrgb) != 0, weighted = (FILTER & kAlphaWeighted) != 0;
@@ -126,7 +75,10 @@ __global__ void __launch_bounds__(256) cvttmi_mipfilter_narrow_kernel(const uint
     dst += blockIdx.z * dstLayer;
     __shared__ SrgbTables tables; // (no LDS is allocated where it is not read)
     if (FILTER & kSrgb)
-        loadSrgbTables(tables);
+    {
+        loadSrgbTables(tables, blockDim.x * blockDim.y, threadIdx.y * blockDim.x + threadIdx.x);
+        __syncthreads();
+    }
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= dstW)
         return;
@@ -149,7 +101,10 @@ __global__ void __launch_bounds__(256) cvttmi_mipfilter_wide_kernel(const uint8_
     dst += blockIdx.z * dstLayer;
     __shared__ SrgbTables tables;
     if (FILTER & kSrgb)
-        loadSrgbTables(tables);
+    {
+        loadSrgbTables(tables, blockDim.x * blockDim.y, threadIdx.y * blockDim.x + threadIdx.x);
+        __syncthreads();
+    }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= chunks)
         return;
@@ -180,24 +135,12 @@ hipError_t launchFiltered(const MipLayers &m, hipStream_t stream)
     return hipGetLastError();
 }
 
-// RGBA8 takes SRGB, NORMAL, BOX | ALPHA_WEIGHTED and SRGB | ALPHA_WEIGHTED, RGBA8_SNORM takes NORMAL; anything else is
-// hipErrorInvalidValue
+// the pairs of withKindFilter; anything else is hipErrorInvalidValue
 hipError_t filteredByKind(const MipLayers &m, int kind, uint32_t filter, hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
-    if (kind == kRGBA8Snorm && filter == kNormal)
-        return launchFiltered<kRGBA8Snorm, kNormal>(m, stream);
-    if (kind != kRGBA8)
-        return hipErrorInvalidValue;
-    switch (filter)
-    {
-    case kSrgb: return launchFiltered<kRGBA8, kSrgb>(m, stream);
-    case kNormal: return launchFiltered<kRGBA8, kNormal>(m, stream);
-    case kAlphaWeighted: return launchFiltered<kRGBA8, kAlphaWeighted>(m, stream);
-    case kSrgb | kAlphaWeighted: return launchFiltered<kRGBA8, kSrgb | kAlphaWeighted>(m, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return withKindFilter(kind, filter, [&](auto k, auto f) { return launchFiltered<k(), f()>(m, stream); });
 }
 } // namespace
 
@@ -206,7 +149,7 @@ extern "C" hipError_t cvttmi_launch_downsample_filtered(const void *d_src, size_
                                                         size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind,
                                                         uint32_t filter, hipStream_t stream)
 {
-    if (layers == 0 || layers > kMipMaxLayers)
+    if (!mipLayersOk(layers))
         return hipErrorInvalidValue;
     return filteredByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, filter, stream);
 }

@@ -150,7 +150,7 @@ hipError_t downsampleByKind(const MipLayers &m, int kind, hipStream_t stream)
 extern "C" hipError_t cvttmi_launch_downsample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,
                                                size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, hipStream_t stream)
 {
-    if (layers == 0 || layers > kMipMaxLayers)
+    if (!mipLayersOk(layers))
         return hipErrorInvalidValue;
     return downsampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, stream);
 }

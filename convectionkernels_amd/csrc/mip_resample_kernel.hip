@@ -12,21 +12,12 @@
 // 48.5 KB a workgroup: three workgroups share a CU.  The taps arrive as kernel arguments (scalar registers).  No scratch.
 // Every product is a 24-bit multiply (__mul24: full rate, where a 32-bit multiply runs at a quarter): a tap is below 2^13, a value
 // or an h' below 2^17 (sRGB: T <= 65535, |h'| <= 78727), and the generator asserts that the sums stay inside int32.
-#include "mip_common.h"
-#include <type_traits>
-
-#define CVTT_SRGB_TABLE __device__ const __attribute__((aligned(16))) // (the byte table is copied a word at a time)
-#include "srgb_tables.h"
+#include "resample_common.h"
 
 namespace
 {
 enum
 {
-    kPlain = 0,
-    kSrgb = 1,
-    kNormal = 2,
-    kWrapRepeat = 0x200,
-    kWrapMirror = 0x400,
     kTileX = 64,
     kTileY = 16
 };
@@ -35,93 +26,6 @@ struct MipTaps
 {
     int w[12];
 };
-
-struct SrgbTables
-{
-    uint32_t next[256]; // [c] = U[c + 1], the threshold above code c; [255] = no sum reaches it
-    uint16_t lin[256];
-    uint8_t coarse[4096];
-};
-
-__device__ __forceinline__ void loadSrgbTables(SrgbTables &t)
-{
-    for (uint32_t i = threadIdx.x; i < 256u; i += 256u)
-    {
-        t.next[i] = i < 255u ? k_srgbThresholds[i] : 0xffffffffu;
-        t.lin[i] = k_srgbToLinear[i];
-    }
-    for (uint32_t i = threadIdx.x; i < 1024u; i += 256u)
-        reinterpret_cast<uint32_t *>(t.coarse)[i] = reinterpret_cast<const uint32_t *>(k_srgbCoarse)[i];
-}
-
-__device__ __forceinline__ uint32_t srgbEncode(const SrgbTables &t, uint32_t S) // S <= 4 * 65535
-{
-    const uint32_t c = t.coarse[S >> 6];
-    return c + (S >= t.next[c] ? 1u : 0u);
-}
-
-// A coordinate that walks along a wrapped axis of n texels: `pos` is the coordinate itself (clamp), its place in the period n
-// (repeat) or in the period 2 n of there-and-back (mirror: ... 1 0 | 0 1 .. n-1 | n-1 .. 0 | 0 ...).  One division where the walk
-// starts, none per step.
-struct Walk
-{
-    int64_t pos;
-    uint32_t n, wrap;
-};
-
-__device__ __forceinline__ Walk walkFrom(int64_t i, uint32_t n, uint32_t wrap)
-{
-    Walk k = {i, n, wrap};
-    if (wrap != 0 && (i < 0 || i >= (int64_t)n))
-    {
-        const uint64_t p = wrap == kWrapMirror ? 2ull * n : (uint64_t)n;
-        k.pos = i >= 0 ? (int64_t)((uint64_t)i % p) : (int64_t)(p - 1u - ((uint64_t)(-i - 1) % p));
-    }
-    return k;
-}
-
-__device__ __forceinline__ uint32_t walkIndex(const Walk &k)
-{
-    if (k.wrap == kWrapMirror)
-        return static_cast<uint32_t>(k.pos < (int64_t)k.n ? k.pos : 2 * (int64_t)k.n - 1 - k.pos);
-    if (k.wrap == kWrapRepeat)
-        return static_cast<uint32_t>(k.pos);
-    return static_cast<uint32_t>(k.pos < 0 ? 0 : k.pos >= (int64_t)k.n ? (int64_t)k.n - 1 : k.pos);
-}
-
-__device__ __forceinline__ void walkStep(Walk &k)
-{
-    k.pos++;
-    if (k.wrap != 0 && k.pos == (k.wrap == kWrapMirror ? 2 * (int64_t)k.n : (int64_t)k.n))
-        k.pos = 0;
-}
-
-// the value channel c of a texel enters the sums with: c = 0..2 under the rule, c = 3 the byte of channel 3, c = 4..6 (NORMAL
-// only) the bytes of channels 0..2
-template <int KIND, int RULE>
-__device__ __forceinline__ int tapValue(const SrgbTables &t, uint32_t texel, int c)
-{
-    const uint32_t v = (texel >> (8 * (c & 3))) & 255u;
-    const int plain = KIND == kRGBA8Snorm ? static_cast<int>(static_cast<int8_t>(v)) : static_cast<int>(v);
-    if (c >= 3 || RULE == kPlain)
-        return plain;
-    if (RULE == kSrgb)
-        return t.lin[v];
-    return KIND == kRGBA8Snorm ? max(plain, -127) : 2 * plain - 255;
-}
-
-// The last step of the plain rule: clamp((s + 2^17) >> 18, 0..255 or -128..127), written as the clamp of the sum followed by the
-// shift (the same value: the shift is monotone).  Shift-then-clamp of two neighbouring channels is what the compiler turns into
-// v_ashr_pk_u8_i32, whose result it then ORs into the texel whole -- on the MI355X the upper half of that register kept what
-// it held before, and channel 2 and alpha of the texel came out wrong.
-template <int KIND>
-__device__ __forceinline__ uint32_t plainByte(int s) // s: the second pass's sum, 18 fraction bits
-{
-    const int t = s + (1 << 17);
-    if (KIND == kRGBA8Snorm)
-        return static_cast<uint32_t>(min(max(t, -(128 << 18)), (128 << 18) - 1) >> 18) & 255u;
-    return static_cast<uint32_t>(min(max(t, 0), (256 << 18) - 1)) >> 18;
-}
 
 template <int KIND, int RULE, int NTAPS>
 __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
@@ -142,7 +46,7 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
     dst += blockIdx.z * dstLayer;
     if (RULE == kSrgb)
     {
-        loadSrgbTables(tables);
+        loadSrgbTables(tables, 256u, threadIdx.x);
         __syncthreads();
     }
     const uint32_t lane = threadIdx.x;
@@ -195,7 +99,7 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
                 int v[kWindow];
 #pragma unroll
                 for (int i = 0; i < kWindow; i++)
-                    v[i] = tapValue<KIND, RULE>(tables, texel[kLead + i], c);
+                    v[i] = ruleValue<KIND, RULE>(texel[kLead + i], c, tables.lin);
 #pragma unroll
                 for (int j = 0; j < 4; j++)
                 {
@@ -285,12 +189,7 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
                         const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
 #pragma unroll
                         for (int c = 0; c < 3; c++)
-                        {
-                            const float q = f[c] / len;
-                            const int r = KIND == kRGBA8Snorm ? min(max(static_cast<int>(floorf(q * 127.0f + 0.5f)), -127), 127)
-                                                              : min(max(static_cast<int>(floorf(q * 127.5f + 128.0f)), 0), 255);
-                            out |= (static_cast<uint32_t>(r) & 255u) << (8 * c);
-                        }
+                            out |= normalByte<KIND>(f[c] / len) << (8 * c);
                     }
                 }
                 if (4u * yg + j < tileH)
@@ -330,27 +229,17 @@ hipError_t resampleByTaps(const MipLayers &m, uint32_t wrap, const MipTaps &taps
     }
 }
 
-// RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL; anything else is hipErrorInvalidValue
+// the pairs of withKindRule; anything else is hipErrorInvalidValue
 hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
-    if (!taps || count > 12u || (wrap != 0 && wrap != kWrapRepeat && wrap != kWrapMirror))
+    if (!taps || count > 12u || !wrapOk(wrap))
         return hipErrorInvalidValue;
     MipTaps t;
     for (uint32_t k = 0; k < 12u; k++)
         t.w[k] = k < count ? taps[k] : 0;
-    if (kind == kRGBA8 && rule == kPlain)
-        return resampleByTaps<kRGBA8, kPlain>(m, wrap, t, count, stream);
-    if (kind == kRGBA8 && rule == kSrgb)
-        return resampleByTaps<kRGBA8, kSrgb>(m, wrap, t, count, stream);
-    if (kind == kRGBA8 && rule == kNormal)
-        return resampleByTaps<kRGBA8, kNormal>(m, wrap, t, count, stream);
-    if (kind == kRGBA8Snorm && rule == kPlain)
-        return resampleByTaps<kRGBA8Snorm, kPlain>(m, wrap, t, count, stream);
-    if (kind == kRGBA8Snorm && rule == kNormal)
-        return resampleByTaps<kRGBA8Snorm, kNormal>(m, wrap, t, count, stream);
-    return hipErrorInvalidValue;
+    return withKindRule(kind, rule, [&](auto k, auto r) { return resampleByTaps<k(), r()>(m, wrap, t, count, stream); });
 }
 } // namespace
 
@@ -360,7 +249,7 @@ extern "C" hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch,
                                              uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule, uint32_t wrap,
                                              const int16_t *taps, uint32_t count, hipStream_t stream)
 {
-    if (layers == 0 || layers > kMipMaxLayers)
+    if (!mipLayersOk(layers))
         return hipErrorInvalidValue;
     return resampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, taps, count, stream);
 }

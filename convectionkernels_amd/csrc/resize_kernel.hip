@@ -18,31 +18,16 @@
 // Every product is a 24-bit multiply: |tap| <= 16385 + what a row is missing, a value or an h' below 2^17 (sRGB: T <= 65535,
 // |h'| <= (65535 P + 8192) >> 14 < 2^17 for the P < 2^15 that cvttmi_resize_taps lets through), and that function has checked that
 // the sums stay inside int32.
-#include "mip_common.h"
-#include <type_traits>
-
-#define CVTT_SRGB_TABLE __device__ const __attribute__((aligned(16))) // (the byte table is copied a word at a time)
-#include "srgb_tables.h"
+#include "resample_common.h"
 
 namespace
 {
 enum
 {
-    kPlain = 0,
-    kSrgb = 1,
-    kNormal = 2,
-    kWrapRepeat = 0x200,
-    kWrapMirror = 0x400,
     kRows = 8,  // two launches: rows of one workgroup
     kTileX = 64, // one launch: the tile of output texels of a workgroup
     kTileY = 16,
     kFusedLdsBytes = 52 * 1024 // ... and the LDS it may take: three workgroups share a CU's 160 KB
-};
-
-struct SrgbTables
-{
-    uint32_t next[256]; // [c] = U[c + 1], the threshold above code c; [255] = no sum reaches it
-    uint8_t coarse[4096];
 };
 
 struct NormalEntry
@@ -56,58 +41,6 @@ struct EntryOf
     typedef typename std::conditional<RULE == kSrgb, int4, typename std::conditional<RULE == kNormal, NormalEntry, short4>::type>::type type;
 };
 
-__device__ __forceinline__ uint32_t srgbEncode(const SrgbTables &t, uint32_t S) // S <= 4 * 65535
-{
-    const uint32_t c = t.coarse[S >> 6];
-    return c + (S >= t.next[c] ? 1u : 0u);
-}
-
-// A coordinate that walks along a wrapped axis of n texels (the walk of mip_resample_kernel.hip): `pos` is the coordinate itself
-// (clamp), its place in the period n (repeat) or in the period 2 n of there-and-back (mirror).  One division where the walk starts.
-struct Walk
-{
-    int64_t pos;
-    uint32_t n, wrap;
-};
-
-__device__ __forceinline__ Walk walkFrom(int64_t i, uint32_t n, uint32_t wrap)
-{
-    Walk k = {i, n, wrap};
-    if (wrap != 0 && (i < 0 || i >= (int64_t)n))
-    {
-        const uint64_t p = wrap == kWrapMirror ? 2ull * n : (uint64_t)n;
-        k.pos = i >= 0 ? (int64_t)((uint64_t)i % p) : (int64_t)(p - 1u - ((uint64_t)(-i - 1) % p));
-    }
-    return k;
-}
-
-__device__ __forceinline__ uint32_t walkIndex(const Walk &k)
-{
-    if (k.wrap == kWrapMirror)
-        return static_cast<uint32_t>(k.pos < (int64_t)k.n ? k.pos : 2 * (int64_t)k.n - 1 - k.pos);
-    if (k.wrap == kWrapRepeat)
-        return static_cast<uint32_t>(k.pos);
-    return static_cast<uint32_t>(k.pos < 0 ? 0 : k.pos >= (int64_t)k.n ? (int64_t)k.n - 1 : k.pos);
-}
-
-__device__ __forceinline__ void walkStep(Walk &k)
-{
-    k.pos++;
-    if (k.wrap != 0 && k.pos == (k.wrap == kWrapMirror ? 2 * (int64_t)k.n : (int64_t)k.n))
-        k.pos = 0;
-}
-
-// the last step of the plain rule, clamp((s + 2^17) >> 18), as the clamp of the sum followed by the shift (mip_resample_kernel.hip
-// says why: shift-then-clamp of neighbouring channels becomes a packed instruction whose upper half came out wrong)
-template <int KIND>
-__device__ __forceinline__ uint32_t plainByte(int s)
-{
-    const int t = s + (1 << 17);
-    if (KIND == kRGBA8Snorm)
-        return static_cast<uint32_t>(min(max(t, -(128 << 18)), (128 << 18) - 1) >> 18) & 255u;
-    return static_cast<uint32_t>(min(max(t, 0), (256 << 18) - 1)) >> 18;
-}
-
 struct ResizeArgs
 {
     const uint8_t *src;
@@ -119,18 +52,6 @@ struct ResizeArgs
     const int32_t *fx, *fy;
     uint32_t nx, ny, wrap;
 };
-
-__device__ __forceinline__ void loadLinear(uint16_t *lin) // 256 lanes
-{
-    lin[threadIdx.x] = k_srgbToLinear[threadIdx.x];
-}
-
-__device__ __forceinline__ void loadEncode(SrgbTables &t) // 256 lanes
-{
-    t.next[threadIdx.x] = threadIdx.x < 255u ? k_srgbThresholds[threadIdx.x] : 0xffffffffu;
-    for (uint32_t i = threadIdx.x; i < 1024u; i += 256u)
-        reinterpret_cast<uint32_t *>(t.coarse)[i] = reinterpret_cast<const uint32_t *>(k_srgbCoarse)[i];
-}
 
 // The horizontal pass of one entry: output column x of one source row.  tap: the column's weights, `stride` apart.
 template <int KIND, int RULE>
@@ -147,6 +68,8 @@ __device__ __forceinline__ typename EntryOf<RULE>::type horizontalEntry(const Re
 #pragma unroll
         for (int c = 0; c < 4; c++)
         {
+            // ruleValue of c and, under NORMAL, of 4 + c, spelled out: through the function the NORMAL instances order their
+            // instructions differently
             const uint32_t v = (texel >> (8 * c)) & 255u;
             const int plain = KIND == kRGBA8Snorm ? static_cast<int>(static_cast<int8_t>(v)) : static_cast<int>(v);
             int value = plain;
@@ -175,7 +98,7 @@ __device__ __forceinline__ typename EntryOf<RULE>::type horizontalEntry(const Re
 
 // The vertical pass of one output texel: at(k) = the entry under tap k, tap[k] its weight.
 template <int KIND, int RULE, class At>
-__device__ __forceinline__ uint32_t verticalTexel(const int16_t *tap, uint32_t ny, const SrgbTables &tables, At at)
+__device__ __forceinline__ uint32_t verticalTexel(const int16_t *tap, uint32_t ny, const SrgbEncodeTables &tables, At at)
 {
     int s[4] = {0, 0, 0, 0};
     for (uint32_t k = 0; k < ny; k++)
@@ -232,12 +155,7 @@ __device__ __forceinline__ uint32_t verticalTexel(const int16_t *tap, uint32_t n
             const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
 #pragma unroll
             for (int c = 0; c < 3; c++)
-            {
-                const float q = f[c] / len;
-                const int r = KIND == kRGBA8Snorm ? min(max(static_cast<int>(floorf(q * 127.0f + 0.5f)), -127), 127)
-                                                  : min(max(static_cast<int>(floorf(q * 127.5f + 128.0f)), 0), 255);
-                out |= (static_cast<uint32_t>(r) & 255u) << (8 * c);
-            }
+                out |= normalByte<KIND>(f[c] / len) << (8 * c);
         }
     }
     return out;
@@ -251,7 +169,7 @@ __global__ void __launch_bounds__(256) cvttmi_resize_fused_kernel(ResizeArgs a, 
     typedef typename EntryOf<RULE>::type Entry;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     Entry *hbuf = reinterpret_cast<Entry *>(lds); // rows x kTileX entries
-    __shared__ SrgbTables tables;                 // (no LDS is allocated where it is not read)
+    __shared__ SrgbEncodeTables tables;           // (no LDS is allocated where it is not read)
     __shared__ uint16_t lin[RULE == kSrgb ? 256 : 1];
     if constexpr (RULE == kSrgb)
     {
@@ -322,7 +240,7 @@ template <int KIND, int RULE>
 __global__ void __launch_bounds__(256) cvttmi_resize_v_kernel(ResizeArgs a)
 {
     typedef typename EntryOf<RULE>::type Entry;
-    __shared__ SrgbTables tables; // (no LDS is allocated where it is not read)
+    __shared__ SrgbEncodeTables tables; // (no LDS is allocated where it is not read)
     if constexpr (RULE == kSrgb)
     {
         loadEncode(tables);
@@ -380,7 +298,7 @@ extern "C" size_t cvttmi_resize_entry_bytes(uint32_t rule)
 extern "C" uint32_t cvttmi_resize_fused_rows(uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny)
 {
     const size_t entry = cvttmi_resize_entry_bytes(rule);
-    const size_t room = kFusedLdsBytes - (rule == kSrgb ? sizeof(SrgbTables) + 512u : 0u);
+    const size_t room = kFusedLdsBytes - (rule == kSrgb ? sizeof(SrgbEncodeTables) + 512u : 0u);
     uint64_t rows = 0;
     for (uint32_t y0 = 0; y0 < dstH; y0 += kTileY)
     {
@@ -401,21 +319,11 @@ extern "C" hipError_t cvttmi_launch_resize(const void *d_src, size_t srcPitch, s
                                            const int16_t *d_wy, const int32_t *d_fy, uint32_t ny, void *d_mid, uint32_t fusedRows,
                                            hipStream_t stream)
 {
-    if (layers == 0 || layers > kMipMaxLayers || srcW == 0 || srcH == 0 || dstW == 0 || dstH == 0 || (srcW | srcH | dstW | dstH) > 65535u || nx == 0 ||
-        ny == 0 || (wrap != 0 && wrap != kWrapRepeat && wrap != kWrapMirror) || !d_wx || !d_fx || !d_wy || !d_fy || (!fusedRows && !d_mid) ||
+    if (!mipLayersOk(layers) || srcW == 0 || srcH == 0 || dstW == 0 || dstH == 0 || (srcW | srcH | dstW | dstH) > 65535u || nx == 0 || ny == 0 ||
+        !wrapOk(wrap) || !d_wx || !d_fx || !d_wy || !d_fy || (!fusedRows && !d_mid) ||
         (size_t)fusedRows * kTileX * cvttmi_resize_entry_bytes(rule) > kFusedLdsBytes)
         return hipErrorInvalidValue;
     const ResizeArgs a = {static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_dst), d_mid, srcPitch, srcLayer, dstPitch, dstLayer,
                           srcW, srcH, dstW, dstH, d_wx, d_wy, d_fx, d_fy, nx, ny, wrap};
-    if (kind == kRGBA8 && rule == kPlain)
-        return launchResize<kRGBA8, kPlain>(a, layers, fusedRows, stream);
-    if (kind == kRGBA8 && rule == kSrgb)
-        return launchResize<kRGBA8, kSrgb>(a, layers, fusedRows, stream);
-    if (kind == kRGBA8 && rule == kNormal)
-        return launchResize<kRGBA8, kNormal>(a, layers, fusedRows, stream);
-    if (kind == kRGBA8Snorm && rule == kPlain)
-        return launchResize<kRGBA8Snorm, kPlain>(a, layers, fusedRows, stream);
-    if (kind == kRGBA8Snorm && rule == kNormal)
-        return launchResize<kRGBA8Snorm, kNormal>(a, layers, fusedRows, stream);
-    return hipErrorInvalidValue;
+    return withKindRule(kind, rule, [&](auto k, auto r) { return launchResize<k(), r()>(a, layers, fusedRows, stream); });
 }

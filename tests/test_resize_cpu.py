@@ -48,6 +48,19 @@ def test_exactly_half_is_the_mip_kernel(kernel):
         assert (first == 2 * np.arange(src // 2) + 1 - 2 * mip_resample_ref.RADIUS[kernel]).all(), src
 
 
+@pytest.mark.parametrize("dst", (1, 3, 8))
+@pytest.mark.parametrize("kernel", sorted(api.MIP_KERNELS))
+def test_the_two_tap_owners_agree_at_half(kernel, dst):
+    """the shim's any-size rule (cvttmi_resize_taps) at src = 2 dst against the generated table of the mip path
+    (cvttmi_mip_kernel_taps): every weight row is that table, and tap 0 lies count / 2 - 1 texels left of texel 2 x"""
+    taps = api.mip_kernel_taps(kernel)
+    first, q = api.resize_taps(2 * dst, dst, kernel)
+    assert q.shape == (dst, len(taps)) and first.shape == (dst,)
+    for x in range(dst):
+        assert (q[x] == taps).all(), x
+        assert first[x] == 2 * x + 1 - len(taps) // 2, x
+
+
 @pytest.mark.parametrize("kernel", KERNEL_NAMES)
 def test_the_same_size_is_the_identity(kernel):
     for src in (1, 2, 7, 64, 257):
