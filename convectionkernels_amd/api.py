@@ -1042,6 +1042,19 @@ class Context:
         self._check(self._lib.cvttmi_selftest_arith(self._h, count, seed, ctypes.byref(d), ctypes.byref(q)), "selftest_arith")
         return int(d.value), int(q.value)
 
+    def selftest_mfma_i8(self, a, b):
+        """(32, 16) int8 . (16, 32) int8 -> (32, 32) int32 by the matrix-core instruction of the BC7 first-tier sums, with the
+        operand maps that kernel relies on (csrc/mfma_i8.h)"""
+        a = np.ascontiguousarray(a, dtype=np.int8)
+        b = np.ascontiguousarray(b, dtype=np.int8)
+        if a.shape != (32, 16) or b.shape != (16, 32):
+            raise CvttError("selftest_mfma_i8 takes a (32, 16) and a (16, 32) int8 array")
+        out = np.empty((32, 32), np.int32)
+        fn = self._lib.cvttmi_selftest_mfma_i8
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._check(fn(self._h, a.ctypes.data, b.ctypes.data, out.ctypes.data), "selftest_mfma_i8")
+        return out
+
     # -- image -> PixelBlock tiling on the device (reference etc2packer.cpp:215-247, 275-281) --
     def tile_image(self, image, stream=None):
         """(H,W,4) CUDA tensor, uint8 (RGBA8) or a 2-byte dtype (RGBA16F bit patterns), rows may be

@@ -732,6 +732,61 @@ __device__ __forceinline__ float subsetBound2D(const Sums2D &m, float rcpN, floa
     return fmaxf(lb, 0.0f);
 }
 
+// =====================================================================================
+// The masked sums of the two-subset sets on the 8-bit grid, by the matrix cores (mfma_i8.h).  They are one integer contraction
+// with a constant left side,
+//   sums[partition][quantity, block] = sum over the 16 pixels of mask[partition][pixel] * feature[pixel][quantity, block],
+// and K = 16 of v_mfma_i32_32x32x16_i8 is the pixels of a block.  The masks are the B operand (0 / 1 bytes, 32 partitions per
+// tile); the features of four blocks are the 32 rows of the A operand, eight per block: u, v, and uu, vv, uv each as
+// lo = x & 127 and hi = x >> 7 (|u|, |v| <= 127, so lo is in [0, 127] and hi in [-127, 126], and the sum is lo + 128 hi summed).
+// Rows are ordered so that a lane of the result holds whole blocks: row = (q & 3) | (block & 1) << 2 | (q >> 2) << 3 |
+// (block >> 1) << 4 puts quantity q of block 2 j + (lane >> 5) of the group in register 8 j + q.  A lane of the result is one
+// partition: its subset sizes and their reciprocals are constants of the tile.
+// Per block the wave shares a record of 16 words in LDS: U[4], V[4] of Proj2D<true>, tU tV tUU tVV, tUV, the block's best
+// error, its static alpha error, one unused.
+// =====================================================================================
+constexpr int kT1RecWords = 16;
+constexpr int kT1AliveAt = 16 * kT1RecWords; // behind the records: bit p of word [tile][block] = partition 32 tile + p stays
+
+// quantity of A-operand row r, and its block within the group of four
+__device__ __forceinline__ constexpr int t1RowQuantity(int r) { return (r & 3) + 4 * ((r >> 3) & 1); }
+__device__ __forceinline__ constexpr int t1RowBlock(int r) { return 2 * (r >> 4) + ((r >> 2) & 1); }
+
+// the B operand of tile `tile` for this lane: pixels 8 h .. 8 h + 7 of partition 32 tile + (lane & 31), one 0 / 1 byte each
+__device__ __forceinline__ u64 t1MaskOperand(u32 mask16, int h)
+{
+    const u32 m8 = (mask16 >> (8 * h)) & 0xffu;
+    const u32 lo = ((m8 & 0xfu) * 0x00204081u) & 0x01010101u;
+    const u32 hi = ((m8 >> 4) * 0x00204081u) & 0x01010101u;
+    return (u64)lo | ((u64)hi << 32);
+}
+
+// the A operand of a group of four blocks for this lane: quantity q of pixels 8 h .. 8 h + 7 of the lane's block (`rec`)
+__device__ __forceinline__ u64 t1FeatureOperand(const u32 *rec, int h, int q)
+{
+    const uint2 U = *reinterpret_cast<const uint2 *>(rec + 2 * h), V = *reinterpret_cast<const uint2 *>(rec + 4 + 2 * h);
+    // q: 0 u, 1 v, 2 3 uu, 4 5 vv, 6 7 uv
+    const bool firstV = (q == 1) | (q == 4) | (q == 5), secondU = (q == 2) | (q == 3);
+    const u32 a[2] = {firstV ? V.x : U.x, firstV ? V.y : U.y};
+    const u32 b[2] = {secondU ? U.x : V.x, secondU ? U.y : V.y};
+    const int sh = (q & 1) ? 7 : 0;
+    const u32 keep = (q & 1) ? 0xffu : 0x7fu;
+    u32 w[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+    {
+        u32 acc = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const int x = __builtin_amdgcn_sbfe((int)a[i], 8 * k, 8), y = __builtin_amdgcn_sbfe((int)b[i], 8 * k, 8);
+            acc |= ((u32)(__mul24(x, y) >> sh) & keep) << (8 * k);
+        }
+        w[i] = (q < 2) ? a[i] : acc;
+    }
+    return (u64)w[0] | ((u64)w[1] << 32);
+}
+
 } // namespace
 
 // bit k of the result = bit 4k + c of m: the partitions sub-lane c of a quad looks after

@@ -221,6 +221,7 @@ __device__ __noinline__ void boundDumpEmit(u32 block, u32 w1, u32 w2, u32 w3, fl
 // chains, the dual-plane search, the partition bounds.  bc7Body below is the kernel.
 #include "bc7_chain.h"
 #include "bc7_dual.h"
+#include "mfma_i8.h"
 #include "bc7_bounds.h"
 
 // HARD = false: the encoder.  A block whose mode-7 stage starts with at least A.hardMin partitions alive hands them to
@@ -918,8 +919,92 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                         makeProjection(lpix, bsL, A, use4, scale, P);
                     }
                     PROF_MARK(7)
+                    bool byMatrix = false;
+                    if constexpr (G8)
+                        byMatrix = boundSet < 2;
+                    if constexpr (G8)
+                    if (byMatrix)
+                    {
+                        // Two subsets on the 8-bit grid: the masked sums come from the matrix cores (bc7_bounds.h, "by the
+                        // matrix cores").  The records of the blocks and the alive words behind them lie in s_res, idle between
+                        // the rounds of one stage and the next.  Lane l of a result is partition 32 tile + (l & 31) of the
+                        // blocks 4 g + 2 j + (l >> 5), j = 0, 1: sixteen bounds per lane, as in the loop below.
+                        u32 *const s_t1 = &s_res[0][0];
+                        if (c == 0)
+                        {
+                            uint4 *const rec = reinterpret_cast<uint4 *>(s_t1 + blk * kT1RecWords);
+                            rec[0] = make_uint4(P.U[0], P.U[1], P.U[2], P.U[3]);
+                            rec[1] = make_uint4(P.V[0], P.V[1], P.V[2], P.V[3]);
+                            rec[2] = make_uint4((u32)P.tU, (u32)P.tV, (u32)P.tUU, (u32)P.tVV);
+                            rec[3] = make_uint4((u32)P.tUV, __builtin_bit_cast(u32, work.err), __builtin_bit_cast(u32, staticErr), 0u);
+                        }
+                        __syncthreads();
+                        const int h = lane >> 5;
+                        u64 maskOp[2];
+                        int n1[2];
+                        float rcp1[2], rcp0[2];
+#pragma unroll
+                        for (int t = 0; t < 2; t++)
+                        {
+                            const u32 m = s_pm2[(lane & 31) + 32 * t];
+                            maskOp[t] = t1MaskOperand(m, h);
+                            n1[t] = __popc(m);
+                            rcp1[t] = __builtin_bit_cast(float, kRcpDown[n1[t]]);
+                            rcp0[t] = __builtin_bit_cast(float, kRcpDown[16 - n1[t]]);
+                        }
+                        const int rowQ = t1RowQuantity(lane & 31);
+                        const u32 *const featRec = s_t1 + t1RowBlock(lane & 31) * kT1RecWords;
+#pragma unroll 1
+                        for (int g = 0; g < 4; g++)
+                        {
+                            const u64 featOp = t1FeatureOperand(featRec + 4 * g * kT1RecWords, h, rowQ);
+#pragma unroll
+                            for (int t = 0; t < 2; t++)
+                            {
+                                const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                                const v16i acc = mfmaI8(featOp, maskOp[t], zero);
+                                const int partition = (lane & 31) + 32 * t;
+#pragma unroll
+                                for (int j = 0; j < 2; j++)
+                                {
+                                    const int block = 4 * g + 2 * j + h;
+                                    const uint4 tot = *reinterpret_cast<const uint4 *>(s_t1 + block * kT1RecWords + 8);
+                                    const uint4 tail = *reinterpret_cast<const uint4 *>(s_t1 + block * kT1RecWords + 12);
+                                    Sums2D s1, s0;
+                                    s1.n = n1[t];
+                                    s1.u = acc[8 * j + 0];
+                                    s1.v = acc[8 * j + 1];
+                                    s1.uu = acc[8 * j + 2] + (int)((u32)acc[8 * j + 3] << 7);
+                                    s1.vv = acc[8 * j + 4] + (int)((u32)acc[8 * j + 5] << 7);
+                                    s1.uv = acc[8 * j + 6] + (int)((u32)acc[8 * j + 7] << 7);
+                                    s0.n = 16 - s1.n;
+                                    s0.u = (int)tot.x - s1.u;
+                                    s0.v = (int)tot.y - s1.v;
+                                    s0.uu = (int)tot.z - s1.uu;
+                                    s0.vv = (int)tot.w - s1.vv;
+                                    s0.uv = (int)tail.x - s1.uv;
+                                    const float blockErr = __builtin_bit_cast(float, tail.y);
+                                    float lb = subsetBound2D<true>(s0, rcp0[t], invScaleSq, twoDelta) + subsetBound2D<true>(s1, rcp1[t], invScaleSq, twoDelta);
+                                    lb += __builtin_bit_cast(float, tail.z); // the static alpha error (lb >= +0: adding 0.0f changes nothing)
+                                    lbStore(partition, block, lb);
+                                    BOUND_DUMP(if (vBlock * 16u + (u32)block < A.numBlocks)
+                                                   boundDumpEmit(vBlock * 16u + (u32)block, BD_TIER1 | (BD_FORM_CMP << 8), (u32)boundSet | ((u32)mode << 8) | ((u32)numSubsets << 16) | (4u << 24),
+                                                                 (u32)partition, lb, lbLoad(partition, block), blockErr, lb > blockErr ? 1u : 0u,
+                                                                 __builtin_bit_cast(float, tail.z), 0.0f, 0.0f, 0.0f));
+                                    // the comparison on the full-precision value, as ballots per block
+                                    const u64 stay = __ballot(!(lb > blockErr));
+                                    if (lane == 0)
+                                        *reinterpret_cast<uint2 *>(s_t1 + kT1AliveAt + 16 * t + 4 * g + 2 * j) = make_uint2((u32)stay, (u32)(stay >> 32));
+                                }
+                            }
+                        }
+                        __syncthreads();
+                        freshAlive = everyFourth((u64)s_t1[kT1AliveAt + blk] | ((u64)s_t1[kT1AliveAt + 16 + blk] << 32), c);
+                        freshBounds = true;
+                        return;
+                    }
                     // the byte masks of the next partition are loaded while this one is computed
-                    const bool two = boundSet < 2;
+                    const bool two = !G8 && boundSet < 2; // (on the 8-bit grid the two-subset sets went to the matrix cores above)
                     auto selOf = [&](int partition, int which) -> uint4 {
                         return *reinterpret_cast<const uint4 *>(T->subsetByteMask[two ? partition : 64 + 2 * partition + which]);
                     };
@@ -942,7 +1027,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
                             if (!two)
                                 selB1 = selOf(nextPartition, 1);
                         }
-                        if (boundSet < 2)
+                        if (two)
                         {
                             Sums2D s1, s0;
                             if constexpr (G8)

@@ -3,6 +3,7 @@
 // kernel evaluates both on pseudo-random bit patterns with exactly the expressions the encoders
 // use (operator/ and sqrtExact, same compiler flags); the host compares with DIVSS / SQRTSS.
 #include "cvtt_kernel_common.h"
+#include "mfma_i8.h"
 
 namespace
 {
@@ -29,7 +30,32 @@ __global__ void cvttmi_selftest_kernel(u64 seed, u64 first, u32 count, u32 *__re
     results[2 * i] = __float_as_uint(fa / fb);
     results[2 * i + 1] = __float_as_uint(sqrtExact(__uint_as_float(a & 0x7fffffffu)));
 }
+
+// One matrix-core product with the operand maps of mfma_i8.h: a (32 x 16) . b (16 x 32), both int8 and row-major, to the
+// row-major 32 x 32 int32 tile `out`.  One wave.
+__global__ void cvttmi_selftest_mfma_i8_kernel(const int8_t *__restrict__ a, const int8_t *__restrict__ b, int *__restrict__ out)
+{
+    const int l = threadIdx.x, rc = l & 31, kh = l >> 5;
+    u64 av = 0, bv = 0;
+#pragma unroll
+    for (int t = 0; t < 8; t++)
+    {
+        av |= (u64)(uint8_t)a[rc * 16 + 8 * kh + t] << (8 * t);
+        bv |= (u64)(uint8_t)b[(8 * kh + t) * 32 + rc] << (8 * t);
+    }
+    v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    acc = mfmaI8(av, bv, acc);
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        out[mfmaRowOf(r, kh) * 32 + rc] = acc[r];
+}
 } // namespace
+
+extern "C" hipError_t cvttmi_launch_selftest_mfma_i8(const void *d_a, const void *d_b, void *d_out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cvttmi_selftest_mfma_i8_kernel, dim3(1), dim3(64), 0, stream, (const int8_t *)d_a, (const int8_t *)d_b, (int *)d_out);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t cvttmi_launch_selftest(uint64_t seed, uint64_t first, uint32_t count, void *d_operands, void *d_results,
                                              hipStream_t stream)
