@@ -1055,6 +1055,15 @@ class Context:
         self._check(fn(self._h, a.ctypes.data, b.ctypes.data, out.ctypes.data), "selftest_mfma_i8")
         return out
 
+    def selftest_endpoint_byte(self):
+        """(mismatches, lowest mismatching bit pattern or None): the BC7 kernels' two-instruction endpoint byte
+        (csrc/cvtt_kernel_common.h, endpointByte) against (int)clampRound(x, 255) on all 2^32 binary32 bit patterns"""
+        fn = self._lib.cvttmi_selftest_endpoint_byte
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        n, first = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._check(fn(self._h, ctypes.byref(n), ctypes.byref(first)), "selftest_endpoint_byte")
+        return int(n.value), (int(first.value) if n.value else None)
+
     # -- image -> PixelBlock tiling on the device (reference etc2packer.cpp:215-247, 275-281) --
     def tile_image(self, image, stream=None):
         """(H,W,4) CUDA tensor, uint8 (RGBA8) or a 2-byte dtype (RGBA16F bit patterns), rows may be

@@ -188,8 +188,8 @@ __device__ __forceinline__ void evalChain(const u32 *lp, u32 mask, u64 list, int
         {
             if (ch < NRC)
             {
-                ep[0][ch] = (int)clampRound(u.base[ch] + u.offset[ch] * tf0, 255.0f);
-                ep[1][ch] = (int)clampRound(u.base[ch] + u.offset[ch] * tf1, 255.0f);
+                ep[0][ch] = endpointByte(u.base[ch] + u.offset[ch] * tf0);
+                ep[1][ch] = endpointByte(u.base[ch] + u.offset[ch] * tf1);
             }
             else
                 ep[0][ch] = ep[1][ch] = 255;
@@ -420,8 +420,8 @@ __device__ __forceinline__ void evalChain(const u32 *lp, u32 mask, u64 list, int
                         p1 = vs[ch] * wRcp;
                         p2 = p1;
                     }
-                    ep[0][ch] = (int)clampRound(p1 * A.rcpW[ch], 255.0f);
-                    ep[1][ch] = (int)clampRound(p2 * A.rcpW[ch], 255.0f);
+                    ep[0][ch] = endpointByte(p1 * A.rcpW[ch]);
+                    ep[1][ch] = endpointByte(p2 * A.rcpW[ch]);
                 }
                 else
                     ep[0][ch] = ep[1][ch] = 0; // overwritten with 255 by compressEndpoints

@@ -109,16 +109,16 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
 #pragma unroll
             for (int ch = 0; ch < 3; ch++)
             {
-                ep[0][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf0, 255.0f);
-                ep[1][ch] = (int)clampRound(uRGB.base[ch] + uRGB.offset[ch] * tf1, 255.0f);
+                ep[0][ch] = endpointByte(uRGB.base[ch] + uRGB.offset[ch] * tf0);
+                ep[1][ch] = endpointByte(uRGB.base[ch] + uRGB.offset[ch] * tf1);
             }
             // TweakAlpha (reference BC67.cpp:815-827)
             const float af0 = T->tweakFactors[alphaPrec - 2][tweak][0];
             const float af1 = T->tweakFactors[alphaPrec - 2][tweak][1];
             const float base = (float)alphaMin;
             const float offs = (float)alphaMax - base;
-            ep[0][3] = (int)clampRound(base + offs * af0, 255.0f);
-            ep[1][3] = (int)clampRound(base + offs * af1, 255.0f);
+            ep[0][3] = endpointByte(base + offs * af0);
+            ep[1][3] = endpointByte(base + offs * af1);
         }
 
         for (int refine = 0; refine < numRefine; refine++)
@@ -412,8 +412,8 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                             p1 = vs[ch] * wRcp16;
                             p2 = p1;
                         }
-                        ep[0][ch] = (int)clampRound(p1 * rrcpW[ch], 255.0f);
-                        ep[1][ch] = (int)clampRound(p2 * rrcpW[ch], 255.0f);
+                        ep[0][ch] = endpointByte(p1 * rrcpW[ch]);
+                        ep[1][ch] = endpointByte(p2 * rrcpW[ch]);
                     }
                 }
                 {
@@ -429,8 +429,8 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                         p1 = vs[3] * wRcp16;
                         p2 = p1;
                     }
-                    ep[0][3] = (int)clampRound(p1, 255.0f);
-                    ep[1][3] = (int)clampRound(p2, 255.0f);
+                    ep[0][3] = endpointByte(p1);
+                    ep[1][3] = endpointByte(p2);
                 }
             }
         }

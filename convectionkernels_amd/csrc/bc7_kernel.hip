@@ -128,14 +128,57 @@ extern "C" int cvttmi_bc7_dup_read(unsigned long long *out)
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7Dup), zero, sizeof(zero)) != hipSuccess) return -1;
     return 0;
 }
-#define PROF_DECL unsigned long long profT = __builtin_readcyclecounter(); unsigned long long profAcc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long profCnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PROF_MARK(slot) { const unsigned long long now = __builtin_readcyclecounter(); profAcc[slot] += now - profT; profT = now; }
+// One record per wave of the encoder's launch (tools/bc7_phase_overlap.py), ten 64-bit words in the buffer that
+// cvttmi_bc7_wave_trace_set names (record = workgroup index; none beyond the capacity).  Lane 0 writes every word with an
+// ordinary store where it arises, so that no time stamp has to live in a register across the search:
+//   0  HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]) | XCC_ID << 32, from s_getreg
+//   1  shader clock at the start     2..4  at PROF_MARK 6 (block loaded and bounded), 0 (dual-plane seeds done = the search starts),
+//   1 (the search is over)           5, 6  begin and end of the wave's longest partition-bounds interval (PROF_MARK 2; 0: none)
+//   7  shader clock at the end       8, 9  the 100 MHz wall clock (s_memrealtime) at the start and at the end
+// The shader clock is compared only among the waves of one SIMD.  The caller zeroes the buffer before the encode.
+__device__ unsigned long long *g_bc7WaveTrace;
+__device__ u32 g_bc7WaveTraceCap;
+extern "C" int cvttmi_bc7_wave_trace_set(void *deviceBuffer, uint32_t capacityRecords)
+{
+    unsigned long long *buf = static_cast<unsigned long long *>(deviceBuffer);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7WaveTrace), &buf, sizeof(buf)) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_bc7WaveTraceCap), &capacityRecords, sizeof(capacityRecords)) != hipSuccess) return -1;
+    return 0;
+}
+#define PROF_REC(word, value) { if (!HARD && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) { unsigned long long *const tb_ = g_bc7WaveTrace; \
+    if (tb_ != nullptr && vBlock < g_bc7WaveTraceCap) tb_[(size_t)vBlock * 10u + (word)] = (value); } }
+#define PROF_TRACE_DECL u32 profB2len = 0; PROF_REC(1, profT) PROF_REC(8, __builtin_amdgcn_s_memrealtime()) \
+    PROF_REC(0, (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32))
+#define PROF_TRACE_MARK(slot) { if ((slot) == 6) PROF_REC(2, now) if ((slot) == 0) PROF_REC(3, now) if ((slot) == 1) PROF_REC(4, now) \
+    if ((slot) == 2 && (u32)(now - profT) > profB2len) { profB2len = (u32)(now - profT); PROF_REC(5, profT) PROF_REC(6, now) } }
+#define PROF_TRACE PROF_REC(7, profT) PROF_REC(9, __builtin_amdgcn_s_memrealtime())
+#define PROF_DECL unsigned long long profT = __builtin_readcyclecounter(); unsigned long long profAcc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long profCnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}; PROF_TRACE_DECL
+#define PROF_MARK(slot) { const unsigned long long now = __builtin_readcyclecounter(); profAcc[slot] += now - profT; PROF_TRACE_MARK(slot) profT = now; }
 #define PROF_FLUSH if (threadIdx.x == 0) { unsigned long long tot = 0; for (int i = 0; i < 16; i++) { atomicAdd(&g_bc7Prof[i], profAcc[i]); tot += profAcc[i]; } \
     int bucket = 63 - __builtin_clzll(tot | 1ull) - 12; bucket = bucket < 0 ? 0 : (bucket > 15 ? 15 : bucket); atomicAdd(&g_bc7Prof[16 + bucket], 1ull); \
     } { unsigned long long wsum[8]; for (int i = 0; i < 8; i++) { unsigned long long v = profCnt[i]; if (i >= 4) { for (int st = 1; st < 64; st <<= 1) v += __shfl_xor(v, st); } wsum[i] = v; } \
     if (threadIdx.x == 0) { for (int i = 0; i < 8; i++) atomicAdd(&g_bc7Prof[32 + i], wsum[i]); \
     const unsigned long long passes = profCnt[2] / 64ull; int pb = 63 - __builtin_clzll(passes | 1ull); pb = pb > 7 ? 7 : pb; atomicAdd(&g_bc7Prof[40 + pb], 1ull); } }
 #define PROF_COUNT(slot, n) { profCnt[slot] += (unsigned long long)(n); }
+// -DCVTT_BC7_PROFILE=2: the wave records alone.  The sums and counters above cost the kernel registers it does not have (the
+// full profile build spills); the records need three scalars, so this build keeps four waves per SIMD without scratch and
+// its waves line up as the default build's do.
+#if CVTT_BC7_PROFILE + 0 == 2
+#undef PROF_DECL
+#undef PROF_MARK
+#undef PROF_COUNT
+#undef PROF_FLUSH
+#undef PROF_STAGE
+#undef PROF_STAGE2
+#undef PROF_STAGE_LANES
+#define PROF_DECL unsigned long long profT = __builtin_readcyclecounter(); PROF_TRACE_DECL
+#define PROF_MARK(slot) { const unsigned long long now = __builtin_readcyclecounter(); PROF_TRACE_MARK(slot) profT = now; }
+#define PROF_COUNT(slot, n)
+#define PROF_FLUSH
+#define PROF_STAGE(stage, slot, n)
+#define PROF_STAGE2(stage, slot, n)
+#define PROF_STAGE_LANES(stage, slot, pred)
+#endif
 extern "C" int cvttmi_bc7_prof_read(unsigned long long *out)
 {
     unsigned long long zero[48] = {0};
@@ -148,6 +191,7 @@ extern "C" int cvttmi_bc7_prof_read(unsigned long long *out)
 #define PROF_MARK(slot)
 #define PROF_COUNT(slot, n)
 #define PROF_FLUSH
+#define PROF_TRACE
 #define PROF_STAGE(stage, slot, n)
 #define PROF_STAGE2(stage, slot, n)
 #define PROF_STAGE_LANES(stage, slot, pred)
@@ -2513,6 +2557,7 @@ __device__ __forceinline__ void bc7Body(const uint8_t *__restrict__ blocks, uint
         }
     }
     PROF_MARK(5)
+    PROF_TRACE
     PROF_FLUSH
 }
 #undef REFRESH_LANE

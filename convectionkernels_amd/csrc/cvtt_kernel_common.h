@@ -85,6 +85,15 @@ __device__ __forceinline__ float clampRound(float v, float hi)
 // tools/cvt_pk_u8_probe.hip checks the identity on all 2^32 bit patterns for hi = 3, 7, 15 on the device.
 __device__ __forceinline__ float clampHigh(float v, float hi) { return fminf(v, hi); }
 
+// An LDR endpoint, (int)clampRound(v, 255.0f), by the same identity at hi = 255, the top of the instruction's own range: two
+// instructions (v_min_f32, v_cvt_pk_u8_f32 into byte 0 of a zero word) for four (v_min_f32, v_max_f32, v_rndne_f32,
+// v_cvt_i32_f32).  The four cases above hold unchanged -- nothing in them used hi < 255: for 0 <= x <= 255 the value rounded to
+// nearest even is an integer in 0..255 (254.5 -> 254, 255 -> 255; above 2^23 no float is left below 255 to round), the saturation
+// is never reached from above because fminf caps at 255, and a NaN becomes 255 before the conversion as it does in clampRound.
+// The whole word is the byte, so the int is the one (int)clampRound gave.  Checked on all 2^32 bit patterns on the device:
+// cvttmi_selftest_endpoint_byte (selftest_kernel.hip, tests/test_endpoint_byte_identity_gpu.py).
+__device__ __forceinline__ int endpointByte(float v) { return (int)__builtin_amdgcn_cvt_pk_u8_f32(fminf(v, 255.0f), 0u, 0u); }
+
 // The rest of clampRound for a value c that clampHigh produced, in the rounds whose index also weights the refiner:
 // rintf(fmaxf(c, 0.0f)), with the rounding first.  fmaxf in another basic block than the v_min_f32 (the wave-uniform
 // `if (!last)` of the dual-plane search stands between the two) makes the compiler canonicalise its operand, a

@@ -49,7 +49,38 @@ __global__ void cvttmi_selftest_mfma_i8_kernel(const int8_t *__restrict__ a, con
     for (int r = 0; r < 16; r++)
         out[mfmaRowOf(r, kh) * 32 + rc] = acc[r];
 }
+
+// endpointByte (cvtt_kernel_common.h) against (int)clampRound(x, 255.0f) on every one of the 2^32 binary32 bit patterns -- NaNs,
+// both infinities, both zeros and denormals included.  2^20 threads, 2^12 patterns each.  result[0] += the patterns that differ,
+// result[1] = min(the lowest such pattern).
+__global__ void cvttmi_selftest_endpoint_byte_kernel(unsigned long long *__restrict__ result)
+{
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long mine = 0, first = 0xffffffffull;
+    for (u32 j = 0; j < 4096u; j++)
+    {
+        const u32 bits = (j << 20) | t;
+        const float x = __uint_as_float(bits);
+        if (endpointByte(x) != (int)clampRound(x, 255.0f))
+        {
+            mine++;
+            first = first < bits ? first : bits;
+        }
+    }
+    if (mine)
+    {
+        atomicAdd(&result[0], mine);
+        atomicMin(&result[1], first);
+    }
+}
 } // namespace
+
+// d_result: two 64-bit words, {0, 0xffffffff} on entry.
+extern "C" hipError_t cvttmi_launch_selftest_endpoint_byte(void *d_result, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cvttmi_selftest_endpoint_byte_kernel, dim3(4096), dim3(256), 0, stream, (unsigned long long *)d_result);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t cvttmi_launch_selftest_mfma_i8(const void *d_a, const void *d_b, void *d_out, hipStream_t stream)
 {
