@@ -1,6 +1,7 @@
 // BC7 dual-plane modes 4 / 5: one (mode, rotation, index selector) configuration per lane quad (evalDual).
 // Part of bc7_kernel.hip (one translation unit), included after bc7_chain.h.
 #pragma once
+#include "bc7_dual_setup.h"
 
 namespace
 {
@@ -20,31 +21,6 @@ struct DualInv
     int rowSq[4], rowVs[4];
     u32 minMax;
 };
-
-typedef unsigned short v2us __attribute__((ext_vector_type(2)));
-
-// The 4 or 8 reconstructed values of one channel, ((64 - w) * e0 + w * e1 + 32) >> 6 for the BC7 weights w of a 2- or
-// 3-bit index (reference IndexSelector.h:90-100), as bytes: tabLo = levels 0..3, tabHi = levels 4..7 (3-bit only).
-// Two levels per instruction in packed 16-bit lanes (every intermediate fits 16 bits).
-__device__ __forceinline__ void levelTable(int e0, int e1, bool threeBit, u32 &tabLo, u32 &tabHi)
-{
-    const u32 base = (u32)((e0 << 6) + 32), delta = (u32)(e1 - e0) & 0xffffu;
-    const v2us BB = __builtin_bit_cast(v2us, base | (base << 16)), DD = __builtin_bit_cast(v2us, delta | (delta << 16));
-    const v2us six = {6, 6};
-    // weight pairs: 2-bit {0, 21}, {43, 64}; 3-bit {0, 9}, {18, 27}, {37, 46}, {55, 64}
-    const u32 w01 = threeBit ? (0u | (9u << 16)) : (0u | (21u << 16));
-    const u32 w23 = threeBit ? (18u | (27u << 16)) : (43u | (64u << 16));
-    const v2us r01 = (__builtin_bit_cast(v2us, w01) * DD + BB) >> six;
-    const v2us r23 = (__builtin_bit_cast(v2us, w23) * DD + BB) >> six;
-    tabLo = __builtin_amdgcn_perm(__builtin_bit_cast(u32, r23), __builtin_bit_cast(u32, r01), 0x06040200u);
-    tabHi = 0;
-    if (threeBit)
-    {
-        const v2us r45 = (__builtin_bit_cast(v2us, 37u | (46u << 16)) * DD + BB) >> six;
-        const v2us r67 = (__builtin_bit_cast(v2us, 55u | (64u << 16)) * DD + BB) >> six;
-        tabHi = __builtin_amdgcn_perm(__builtin_bit_cast(u32, r67), __builtin_bit_cast(u32, r45), 0x06040200u);
-    }
-}
 
 // One group of four pixels (16 bytes) of the block's copy in LDS, at the byte address `addr` of the LDS segment.
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
@@ -160,10 +136,7 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                 const float aDW = (float)ep[1][3] - origin[3];
                 const float aLen = safeDenom(aDW * aDW);
                 axis[3] = aDW * (alphaMaxV / aLen);
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    levelTable(ep[0][ch], ep[1][ch], rgbPrec == 3, tabLo[ch], tabHi[ch]);
-                levelTable(ep[0][3], ep[1][3], alphaPrec == 3, tabLo[3], tabHi[3]);
+                dualLevelTables(ep, rgbPrec == 3, alphaPrec == 3, tabLo, tabHi);
             }
             const v2f org01 = {origin[0], origin[1]}, org23 = {origin[2], origin[3]};
             const v2f ax01 = {axis[0], axis[1]}, ax23 = {axis[2], axis[3]};
@@ -175,8 +148,15 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
             // follows it.)
             u32 s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0}; // fast indexing: sum(rec * px), sum(rec^2) per channel
             float slowRGB = 0.0f, slowA = 0.0f;               // slow indexing: the error of the chosen candidates
-            v2f tv01 = {0.0f, 0.0f}, tv23 = {0.0f, 0.0f};
-            v2f tt2 = {0.0f, 0.0f}, ts2 = {0.0f, 0.0f}; // {RGB plane, alpha plane}
+            // the refiner's sums.  Fast indexing starts them from pixel 0's contribution (below) and leaves them unset in the last
+            // round, which neither writes nor reads them
+            v2f tv01, tv23;
+            v2f tt2, ts2; // {RGB plane, alpha plane}
+            if constexpr (!FAST)
+            {
+                tv01 = tv23 = v2f{0.0f, 0.0f};
+                tt2 = ts2 = v2f{0.0f, 0.0f};
+            }
             u32 rgbLo = 0, rgbHi = 0, aLo = 0, aHi = 0; // 4 bits per pixel, pixel p in slot dualIndexSlot(p)
 
             // an address the optimiser cannot see through: the loads stay inside the round (hoisted, they would hold 16
@@ -223,10 +203,28 @@ __device__ __forceinline__ void evalDual(const u32 *sP, const DualInv &inv, int 
                             const v2f t2 = f2 * rcpMax2;
                             const v2f tt = {t2.x, t2.x};
                             const v2f v01 = x01 * w01, v23 = x23 * w23;
-                            tv01 = tv01 + tt * v01;
-                            tv23 = tv23 + t2 * v23;
-                            tt2 = tt2 + t2 * t2;
-                            ts2 = ts2 + t2;
+                            if (g == 0 && k == 0)
+                            {
+                                // Pixel 0 starts the sums instead of being added to +0: no v_add_f32 0, x (which IEEE forbids the
+                                // compiler to drop) and no zeroing.  t2 >= +0 (roundClampLow gives +0 or more, rcpMax2 > 0), so
+                                // t2 * t2 and t2 are >= +0 and 0 + x is x bit for bit; so is tt * v with weights >= +0, and a NaN
+                                // product is quiet already.  Only a negative (or -0) weight can make tt * v a -0 that 0 + x would turn
+                                // into +0.  The sum then still differs only while every later term is -0 as well (one +0 or non-zero
+                                // term and both forms agree), so as -0 for +0, and that sign ends in the solve: with
+                                // z = ts * vs * wRcp16, tv - z is -z for z != 0 and +0 for z = -0 either way; for z = +0 (vs = +0) the
+                                // quotient a = +-0 leaves b = (vs - a * ts) * wRcp16 = +0 and a + b = +0, the two end points.
+                                tv01 = tt * v01;
+                                tv23 = t2 * v23;
+                                tt2 = t2 * t2;
+                                ts2 = t2;
+                            }
+                            else
+                            {
+                                tv01 = tv01 + tt * v01;
+                                tv23 = tv23 + t2 * v23;
+                                tt2 = tt2 + t2 * t2;
+                                ts2 = ts2 + t2;
+                            }
                         }
                     }
                     // the bytes as they are, the odd group in the high nibbles (dualIndexSlot): every index is below 8
