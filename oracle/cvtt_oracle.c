@@ -1561,6 +1561,7 @@ int orc_encode_bc7_sites(uint8_t *out, const uint8_t *blocks, size_t numBlocks, 
 #include "cvtt_oracle_s3tc.inc"
 #include "cvtt_oracle_bc6h.inc"
 #include "cvtt_oracle_etc2.inc"
+#include "cvtt_oracle_etc_parts.inc"
 
 /* ------------------------------------------------------------------------------------
  * the same encodes, also handing out each block's final error: the score of the candidate whose bytes are written.

@@ -104,6 +104,13 @@ int orc_encode_s3tc_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, c
 int orc_encode_etc2_err(uint8_t *out, const uint8_t *blocks, size_t numBlocks, const orc_options *options,
                         const orc_options *allocOptions, int mode, int threads, float *colorErr, uint32_t *alphaErr);
 
+/* ---- the small ETC functions one at a time (cvtt_oracle_etc_parts.inc; the parts, variants and domains: etc_parts.h) ----
+ * chunks [firstChunk, firstChunk + numChunks) of a sweep: checksums, results in full (either may be NULL) and the count of
+ * results that carry ETCP_FLAG; or the results of listed inputs.  -1: no such part, chunk or input. */
+int orc_etc_parts(int part, int variant, const float *weights3, const int32_t *table, uint32_t firstChunk, uint32_t numChunks,
+                  uint64_t *sums, uint32_t *full, uint64_t *flagged, int threads);
+int orc_etc_parts_at(int part, int variant, const float *weights3, const int32_t *table, const uint32_t *inputs, size_t count, uint32_t *out);
+
 /* ---- group-coupling site switch (tests/test_group_coupling.py, tools/find_coupling_witnesses.py) ----
  * Each bit makes ONE semantic AnySet / AllSet site of SURVEY App. B behave the way an encoder that got it wrong would:
  * the horizontal test sees the block's own flag (or count) only, never its seven group mates'.  Block l of a group is

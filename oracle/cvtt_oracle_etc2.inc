@@ -6,7 +6,7 @@
  * CompressETC2AlphaBlockInternal 1902-2085, QuantizeETC2Alpha 2366-2411, chroma axes 3117-3145.
  * Canonical oracle semantics (SURVEY App. C): hazard H2 -- the T-mode candidate slot just past a
  * lane's unique colours reads as 0 when another lane of the group has more unique colours.
- * ETC_UseFakeBT709 is rejected by the entry point (out of scope, SURVEY 8 a17). */
+ * ETC_UseFakeBT709 and ETC_FakeBT709Accurate are restated too (etc_ctx_t.fake / fakeAccurate). */
 #include "cvtt_oracle_etc_tables.h"
 #include "cvtt_oracle_fake709.h"
 

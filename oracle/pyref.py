@@ -394,3 +394,89 @@ class OracleLib:
         if rc != 0:
             raise RuntimeError("orc_encode_bc1 rc=%d" % rc)
         return out.reshape(n, 8)
+
+
+# ---- the small ETC functions one at a time (etc_parts.h; tests/etc_parts.py builds the tables) ----
+ETC_PARTS = {"resolve_th": 0, "resolve_half": 1, "err_fake": 2, "err_wu": 3, "err2": 4, "planar": 5, "emit_t": 6, "emit_h": 7}
+ETC_PARTS_CHUNK = 4096
+
+
+def etc_parts_chunks(part, variant):
+    """etcp_chunks of etc_parts.h"""
+    p = ETC_PARTS[part]
+    if p == 0:
+        return (16 << 21) // ETC_PARTS_CHUNK
+    if p == 1:
+        return (1 << 28) // ETC_PARTS_CHUNK
+    if p in (2, 3, 4):
+        return (1 << 30) // ETC_PARTS_CHUNK
+    if p == 5:
+        return 1
+    return ((1 << 20) if variant & 2 else (1 << 28)) // ETC_PARTS_CHUNK
+
+
+def _etc_parts_args(part, variant, weights, table):
+    w = np.ascontiguousarray(weights if weights is not None else (0.0, 0.0, 0.0), np.float32)
+    t = np.ascontiguousarray(table if table is not None else np.zeros(1, np.int32), np.int32)
+    assert w.size == 3
+    return w, t, (ctypes.c_int(ETC_PARTS[part]), ctypes.c_int(variant), w.ctypes.data_as(ctypes.c_void_p), t.ctypes.data_as(ctypes.c_void_p))
+
+
+def _etc_parts(fn, part, variant, weights, table, first_chunk, num_chunks, full, threads):
+    w, t, head = _etc_parts_args(part, variant, weights, table)
+    sums = np.empty(num_chunks, np.uint64)
+    res = np.empty(num_chunks * ETC_PARTS_CHUNK, np.uint32) if full else None
+    flagged = ctypes.c_uint64(0)
+    fn.restype = ctypes.c_int
+    rc = fn(*head, ctypes.c_uint32(first_chunk), ctypes.c_uint32(num_chunks), sums.ctypes.data_as(ctypes.c_void_p),
+            res.ctypes.data_as(ctypes.c_void_p) if full else None, ctypes.byref(flagged), ctypes.c_int(threads))
+    if rc != 0:
+        raise ValueError("%s: no such part or chunk (%s, %d, %d + %d)" % (fn.__name__, part, variant, first_chunk, num_chunks))
+    return sums, res, int(flagged.value)
+
+
+def _etc_parts_at(fn, part, variant, weights, table, inputs):
+    w, t, head = _etc_parts_args(part, variant, weights, table)
+    inputs = np.ascontiguousarray(inputs, np.uint32)
+    out = np.empty(inputs.size, np.uint32)
+    fn.restype = ctypes.c_int
+    rc = fn(*head, inputs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(inputs.size), out.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise ValueError("%s: no such part or input (%s, %d)" % (fn.__name__, part, variant))
+    return out
+
+
+def _oracle_etc_parts(self, part, variant=0, weights=None, table=None, first_chunk=0, num_chunks=None, full=False, threads=1):
+    """chunks [first_chunk, first_chunk + num_chunks) of a sweep (default: all): (checksums, the results in full or None, the
+    number of results that carry the range flag)"""
+    n = etc_parts_chunks(part, variant) - first_chunk if num_chunks is None else num_chunks
+    return _etc_parts(self.lib.orc_etc_parts, part, variant, weights, table, first_chunk, n, full, threads)
+
+
+def _oracle_etc_parts_at(self, part, inputs, variant=0, weights=None, table=None):
+    return _etc_parts_at(self.lib.orc_etc_parts_at, part, variant, weights, table, inputs)
+
+
+OracleLib.etc_parts = _oracle_etc_parts
+OracleLib.etc_parts_at = _oracle_etc_parts_at
+
+
+class RefEtcParts:
+    """oracle/_ref/libcvtt_ref_etcparts.so -- the reference's own functions behind the same two calls (ref_etc_parts.cpp)"""
+    PATH = os.path.join(HERE, "_ref", "libcvtt_ref_etcparts.so")
+
+    def __init__(self):
+        if not os.path.exists(self.PATH):
+            raise FileNotFoundError(self.PATH)
+        self.lib = ctypes.CDLL(self.PATH)
+
+    @classmethod
+    def available(cls):
+        return os.path.exists(cls.PATH)
+
+    def etc_parts(self, part, variant=0, weights=None, table=None, first_chunk=0, num_chunks=None, full=False, threads=1):
+        n = etc_parts_chunks(part, variant) - first_chunk if num_chunks is None else num_chunks
+        return _etc_parts(self.lib.ref_etc_parts, part, variant, weights, table, first_chunk, n, full, threads)
+
+    def etc_parts_at(self, part, inputs, variant=0, weights=None, table=None):
+        return _etc_parts_at(self.lib.ref_etc_parts_at, part, variant, weights, table, inputs)

@@ -146,6 +146,30 @@ def simple_case(kind):
     return (kind + "_default", kind, blocks, _bytes(api.Options()), None)
 
 
+def etc_options():
+    """the option sets that reach the FAKE instantiations of the ETC kernel (table and accurate rounding, with and without the
+    uniform metric under it) and the two non-default weighted metrics"""
+    F = api.Flags
+    return {"fake": api.Options(flags=F.Default | F.ETC_UseFakeBT709),
+            "fake_accurate": api.Options(flags=F.Ultra | F.ETC_UseFakeBT709),
+            "fake_uniform": api.Options(flags=F.Default | F.ETC_UseFakeBT709 | F.Uniform),
+            "uniform": api.Options(flags=F.Default | F.Uniform),
+            "weights": api.Options(redWeight=0.1, greenWeight=1.0, blueWeight=0.8, alphaWeight=1.0)}
+
+
+@functools.lru_cache(maxsize=None)
+def etc_option_blocks(punchthrough):
+    """etc_blocks plus the content that keeps the T mode's larger distances alive under the fake-BT.709 metric"""
+    return np.concatenate([etc_blocks(punchthrough), content.fake709_t_blocks(8804)])
+
+
+def etc_option_cases(kind=None):
+    """every ETC colour format on its directed content under etc_options().  Not part of all_cases(): tests/golden/mode_census.npz
+    holds the default Options only"""
+    return [("%s_%s" % (k, on), k, etc_option_blocks(k == "etc2punchthrough"), _bytes(o), None)
+            for k in ETC_KINDS if kind in (None, k) for on, o in etc_options().items()]
+
+
 def all_cases():
     out = []
     for key in bc7_sets():

@@ -572,3 +572,30 @@ def r11_narrow_blocks(seed, n, signed):
     base = rng.integers(lo + 20, hi - 20, (n, 1))
     width = rng.integers(1, 16, (n, 1))
     return np.clip(base + rng.integers(-15, 16, (n, 16)) * width // 15, lo, hi).astype(np.int16)
+
+
+def fake709_t_blocks(seed, per=32):
+    """(5 per, 16, 4) uint8, opaque: content on which the ETC2 T mode wins under ETC_UseFakeBT709 with the WEIGHTED metric below
+    it, at the five largest distances (table 3 ... 7).  The reference measures a T block's three line paints with the plain
+    weighted metric even there (ETC.cpp:600) -- paint * weight against pixels that hold luma / chroma -- so a paint only scores
+    where the pixel's fake-BT.709 image equals the paint times the weights.  Mixed content meets that on near-black blocks
+    alone, where the small distances win.  Here it is met by construction: a line colour L = (17 a, 17 b, 17 c) with little
+    green, its paints L - d, L, L + d, and as pixels the colours whose luma / chroma are those paints times the default
+    weights (the inverse conversion, rounded); one to four pixels of another colour are the isolated ones."""
+    rng = _rng(seed)
+    weights = np.array([0.2125 / 0.7154, 1.0, 0.0721 / 0.7154])
+    blocks = np.zeros((5 * per, 16, 4), np.uint8)
+    blocks[..., 3] = 255
+    for i in range(5 * per):
+        d = (16, 23, 32, 41, 64)[i // per]
+        top = min(16, 8 * d // 17 + 1)  # red and blue below 8 d: brighter lines go to the larger distances
+        line = 17 * np.array([rng.integers(0, top), rng.integers(0, 3), rng.integers(0, top)])
+        yuv = np.clip(np.stack([line - d, line, line + d]), 0, 255) * weights
+        y, u, v = yuv[:, 0] * 0.57735026466774571071, yuv[:, 1], yuv[:, 2]
+        rgb = np.stack([y + u * 1.5748000207960953486, y - u * 0.46812425854364753669 - v * 0.26491652528157560861,
+                        y + v * 2.6242146882856944069], axis=-1)
+        rgb = np.clip(np.rint(rgb), 0, 255)
+        px = rgb[rng.choice(3, 16, p=rng.dirichlet([1, 1, 1]))]
+        px[rng.choice(16, int(rng.integers(1, 5)), replace=False)] = rng.integers(0, 256, 3)
+        blocks[i, :, :3] = px
+    return blocks

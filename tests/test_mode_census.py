@@ -415,7 +415,11 @@ def test_census_etc(oracle_out, kind):
     CompressETC1BlockInternal with punchthrough = true for every ETC2 format, which starts its loop over the two codings at
     the differential one), so no content can make it win there; half-blocks with far-apart bases and four luma levels each
     -- where individual beats differential and H in ETC1 -- were tried and gave T / H.  ETC1 emits it, and is required to."""
-    out = oracle_out(C.simple_case(kind))
+    _assert_etc_census(oracle_out(C.simple_case(kind)), kind)
+
+
+def _assert_etc_census(out, kind):
+    """the conditions of test_census_etc on one case's expected bytes"""
     off = 8 if kind == "etc2rgba" else 0
     pt = kind == "etc2punchthrough"
     lay, flip = F.etc_layout(out, off, pt), F.etc_flip(out, off)
@@ -431,6 +435,32 @@ def test_census_etc(oracle_out, kind):
     if pt:
         assert set(F.etc_opaque(out).tolist()) == {0, 1}
         assert F.etc_modes(out, 0, True)["opaque0"].sum() >= 16
+
+
+ETC_OPTION_CASES = [c[0] for c in C.etc_option_cases()]
+
+
+def _etc_option_case(name):
+    return next(c for c in C.etc_option_cases() if c[0] == name)
+
+
+@pytest.mark.parametrize("name", ETC_OPTION_CASES)
+def test_etc_option_case_oracle_equals_reference(oracle_lib, ref_lib, name):
+    """the FAKE instantiations, the uniform and the re-weighted metric on directed content: the restatement stays the reference"""
+    case = _etc_option_case(name)
+    assert_same_blocks(C.encode_oracle(oracle_lib, case, None, _threads()), C.encode_reference(ref_lib, case), case[1],
+                       "restatement vs reference, " + name)
+
+
+@pytest.mark.parametrize("name", ETC_OPTION_CASES)
+def test_census_etc_option_case(oracle_out, name):
+    """every ETC format under every option set of census_cases.etc_options still emits every layout it can x both flips, every
+    T / H distance and, punch-through, both opacities: the conditions of test_census_etc, unchanged.  The fake-BT.709 metric
+    with weights below it starves the T mode of its larger distances on the default content (the reference scores the line
+    paints with the weighted metric against luma / chroma: only near-black blocks survive); content.fake709_t_blocks puts
+    them back for these cases."""
+    case = _etc_option_case(name)
+    _assert_etc_census(oracle_out(case), case[1])
 
 
 @pytest.mark.parametrize("kind", C.EAC_KINDS)
@@ -521,6 +551,19 @@ def test_gpu_ldr_directed(gpu_ctx, expect, kind):
     gpu_ctx.set_rcp_table(expect.rcp)
     case = C.simple_case(kind)
     _gpu_both_paths(gpu_ctx, case, expect(case), "%s vs %s" % (case[0], expect.kind))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ETC_OPTION_CASES)
+def test_gpu_etc_option_case(gpu_ctx, expect, name):
+    """the FAKE instantiations of the ETC kernel (table and accurate rounding), the uniform and the re-weighted metric on content
+    that reaches every mode under them: host array and device tensor, the whole set, one group and nine"""
+    gpu_ctx.set_rcp_table(expect.rcp)
+    case = _etc_option_case(name)
+    exp = expect(case)
+    _gpu_both_paths(gpu_ctx, case, exp, "%s vs %s" % (name, expect.kind))
+    for n in (8, 72):
+        _gpu_both_paths(gpu_ctx, case[:2] + (case[2][:n],) + case[3:], exp[:n], "%s, first %d blocks" % (name, n))
 
 
 @pytest.mark.gpu
