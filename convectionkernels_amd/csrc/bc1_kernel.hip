@@ -10,6 +10,7 @@
 // non-exhaustive path has no cross-lane coupling), every loop is wave-uniform
 // and the reference's sequential strict-'<' commit order is simply program order.
 #include "cvtt_kernel_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -54,6 +54,7 @@
 #include "cvtt_kernel_common.h"
 #include <hip/hip_fp16.h>
 #include <type_traits>
+#include "cvtt_launchers.h"
 
 // Developer-only counters (-DCVTT_BC6H_PROFILE): [0] partition searches (per wave), [1] subset passes run again after a late
 // duplicate, [2] lazy partitions, [3] lazy partitions with a replay, [4] replayed round slots, [5] eager partitions,

@@ -4,9 +4,10 @@
 
 namespace
 {
-// ceil(n / 31) for 0 <= n < 2^23: one v_mul_hi_u32.  2216757579 = (2^36 + 8213) / 31 (NOT ceil(2^36 / 31) = 2216757315):
+// ceil(n / 31), exact for 0 <= n < 8 367 148: one v_mul_hi_u32.  2216757579 = (2^36 + 8213) / 31 (NOT ceil(2^36 / 31) = 2216757315):
 // x * 2216757579 / 2^36 = x / 31 + x * 8213 / (31 * 2^36), and x / 31 lies at least 1 / 31 below the next integer, so the
-// floor is that of x / 31 while x * 8213 < 2^36, i.e. for x < 8.3 million (tools/check_bc6h_quantize.py compares every value)
+// floor is that of x / 31 while x * 8213 < 2^36 where x = n + 30 = 30 (mod 31); n = 8 367 148 is the first to come out one too
+// high (swept on the device; the callers pass at most 31743 * 64)
 __device__ __forceinline__ int ceilDiv31(int n)
 {
     return (int)(__umulhi((u32)(n + 30), 2216757579u) >> 4);
@@ -96,7 +97,8 @@ __device__ __forceinline__ float twosCLHalfToFloatBits(int v16)
 
 // For every finite non-negative half pattern (all the unsigned format ever sees: inputs are
 // clamped to [0, 0x7BFF], reconstructions to <= 31743) the function above equals the hardware
-// conversion, except that it halves denormals (exponent field 0) -- checked exhaustively.
+// conversion, except that it halves denormals (exponent field 0) -- checked exhaustively.  Outside the claim: pattern 0x8000
+// (the conversion keeps -0, the bit manipulation gives +0) and exponent field 31 (infinities and NaNs against 65536 ... 131008).
 template <bool SIGNED>
 __device__ __forceinline__ float twosCLHalfToFloat(int v16)
 {

@@ -76,6 +76,7 @@ constexpr float kBoundGrid8 = 124.0f, kBoundLimit8 = 127.0f;
 #endif
 
 #include "cvtt_kernel_common.h"
+#include "cvtt_launchers.h"
 
 // candidates a block may offer per round when 1 / 2 / <=4 / <=8 blocks of the wave offer at all
 #ifndef CVTT_SPEC_1

@@ -8,6 +8,7 @@
 #include <type_traits>
 #include <utility>
 #include "decode_texels.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "etc2_wave.h"
 #include "etc2_metric.h"
+#include "cvtt_launchers.h"
 
 namespace
 {
@@ -616,7 +617,7 @@ __global__ __launch_bounds__(64, MODE == 2 ? 4 : CVTT_ETC2_WAVES) void cvttmi_et
             isoTargets[ch] = numerator;
         }
         if (FAKE)
-            resolveTHFake(isoQ, isoTargets, numIsolated); // may push a channel to 16 (ETC.cpp:453-454)
+            resolveTHFake(isoQ, isoTargets, numIsolated); // ETC.cpp:453-454; never leaves 0 .. 15 over the swept domain
 #pragma unroll
         for (int ch = 0; ch < 3; ch++)
             isoColor[ch] = isoQ[ch] | (isoQ[ch] << 4);

@@ -8,6 +8,7 @@
 // output texel twelve 16-bit reads of T and, per channel, one byte of C[S >> 6] = encode(S with its low six bits cleared) and one
 // threshold -- U's steps are above 64, so S passes at most one threshold more than its bucket's start.  No scratch.
 #include "resample_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

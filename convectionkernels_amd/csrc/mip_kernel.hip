@@ -10,6 +10,7 @@
 // store.  It runs when both row starts, both pitches and the output width allow 16-byte accesses; everything else takes the
 // narrow kernel, one output texel per lane with texel-sized accesses.  No LDS, no scratch.
 #include "mip_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -13,6 +13,7 @@
 // Every product is a 24-bit multiply (__mul24: full rate, where a 32-bit multiply runs at a quarter): a tap is below 2^13, a value
 // or an h' below 2^17 (sRGB: T <= 65535, |h'| <= 78727), and the generator asserts that the sums stay inside int32.
 #include "resample_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -19,6 +19,7 @@
 // |h'| <= (65535 P + 8192) >> 14 < 2^17 for the P < 2^15 that cvttmi_resize_taps lets through), and that function has checked that
 // the sums stay inside int32.
 #include "resample_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

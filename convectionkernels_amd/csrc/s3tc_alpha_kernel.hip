@@ -6,6 +6,7 @@
 // cross-lane coupling (its AnySet / AllSet only skip duplicate work, and a weighted refiner contribution
 // with weight 1.0 equals an unweighted one), every loop is wave-uniform.
 #include "cvtt_kernel_common.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -4,6 +4,7 @@
 // use (operator/ and sqrtExact, same compiler flags); the host compares with DIVSS / SQRTSS.
 #include "cvtt_kernel_common.h"
 #include "mfma_i8.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "cvtt_device.h"
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -8,6 +8,7 @@
 // neighbouring blocks, so reads are contiguous along the image row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cvtt_launchers.h"
 
 namespace
 {

@@ -519,7 +519,7 @@ static int tmode_unique(const etc_ctx_t *cx, const tmode_setup_t *ts, int table,
             targets[ch] = numerator;
         }
         if (cx->fake)
-            etc_resolve_th_fake(q, targets, ts->numLine); /* ETC.cpp:511-531; may push a channel to 16 */
+            etc_resolve_th_fake(q, targets, ts->numLine); /* ETC.cpp:511-531; never leaves 0 .. 15 over the swept domain (DESIGN.md 2.1) */
         for (int ch = 0; ch < 3; ch++)
             packed |= q[ch] << (ch * 5);
         if (n == 0 || packed != colors[n - 1])

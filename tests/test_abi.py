@@ -28,6 +28,19 @@ def test_library_exports_every_declared_symbol():
     assert set(api.exported_symbols()) <= set(names)
 
 
+def test_dynamic_symbols_are_the_parents():
+    """`nm -D --defined-only` of the built library, sorted, against tests/golden/exports.txt -- the list of the library before its
+    host side was cut into one file per concern: the cut gains and loses no name.  Compared are type letter and name; the address
+    column is dropped, and so are the `__hip_cuid_<hash>` markers the compiler adds, one per translation unit, whose names are
+    hashes of the unit's path."""
+    from convectionkernels_amd import api
+    out = subprocess.check_output(["nm", "-D", "--defined-only", api._LIB_PATH]).decode()
+    names = sorted(" ".join(line.split()[1:]) for line in out.splitlines() if line.strip() and " __hip_cuid_" not in line)
+    want = open(os.path.join(ROOT, "tests", "golden", "exports.txt")).read().splitlines()
+    assert len(want) > 200
+    assert names == want, (sorted(set(names) - set(want)), sorted(set(want) - set(names)))
+
+
 def test_pod_layouts():
     from convectionkernels_amd import api
     lib = api.load_library()
