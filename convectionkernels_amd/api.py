@@ -409,16 +409,26 @@ def mip_filter_value(filter):
 # mip kernels and wrap modes (include/cvtt_mi355x.h CVTTMI_MIP_KERNEL_*, CVTTMI_MIP_WRAP_*): two more fields of the filter word
 MIP_KERNELS = {"triangle": 0x10, "mitchell": 0x20, "lanczos3": 0x30, "kaiser": 0x40}
 MIP_WRAPS = {"clamp": 0, "repeat": 0x200, "mirror": 0x400}
+# the range of an RGBA16F image under a kernel or in a resize (CVTTMI_MIP_HDR_*): what the results are clamped to
+MIP_HDR = {"nonnegative": 0x1000, "signed": 0x2000}
 
 
-def mip_filter_word(filter, kernel=None, wrap="clamp"):
-    """the `filter` value of the C calls: mip_filter_value(filter) with the kernel (a name of MIP_KERNELS or None = the 2x2 rule)
-    and the wrap mode (a name of MIP_WRAPS) OR-ed on"""
+def _hdr_value(hdr):
+    if hdr is None:
+        return 0
+    if hdr not in MIP_HDR:
+        raise CvttError("unknown hdr range %r (one of %s, or None)" % (hdr, ", ".join(MIP_HDR)))
+    return MIP_HDR[hdr]
+
+
+def mip_filter_word(filter, kernel=None, wrap="clamp", hdr=None):
+    """the `filter` value of the C calls: mip_filter_value(filter) with the kernel (a name of MIP_KERNELS or None = the 2x2 rule),
+    the wrap mode (a name of MIP_WRAPS) and the range of an RGBA16F image under a kernel (a name of MIP_HDR or None) OR-ed on"""
     if kernel is not None and kernel not in MIP_KERNELS:
         raise CvttError("unknown mip kernel %r (one of %s)" % (kernel, ", ".join(MIP_KERNELS)))
     if wrap not in MIP_WRAPS:
         raise CvttError("unknown wrap mode %r (one of %s)" % (wrap, ", ".join(MIP_WRAPS)))
-    return mip_filter_value(filter) | (MIP_KERNELS[kernel] if kernel is not None else 0) | MIP_WRAPS[wrap]
+    return mip_filter_value(filter) | (MIP_KERNELS[kernel] if kernel is not None else 0) | MIP_WRAPS[wrap] | _hdr_value(hdr)
 
 
 def mip_kernel_taps(name):
@@ -438,15 +448,16 @@ RESIZE_KERNELS = dict(MIP_KERNELS, box=0)
 RESIZE_RULES = {"box": MIP_FILTER_BOX, "srgb": MIP_FILTER_SRGB, "normal": MIP_FILTER_NORMAL}
 
 
-def resize_filter_word(kernel="lanczos3", filter="box", wrap="clamp"):
-    """the `filter` value of the resize calls: rule (a name of RESIZE_RULES or its value) | kernel (a name of RESIZE_KERNELS) | wrap"""
+def resize_filter_word(kernel="lanczos3", filter="box", wrap="clamp", hdr=None):
+    """the `filter` value of the resize calls: rule (a name of RESIZE_RULES or its value) | kernel (a name of RESIZE_KERNELS) | wrap
+    | the range of an RGBA16F image (a name of MIP_HDR or None)"""
     if kernel not in RESIZE_KERNELS:
         raise CvttError("unknown resize kernel %r (one of %s)" % (kernel, ", ".join(RESIZE_KERNELS)))
     if wrap not in MIP_WRAPS:
         raise CvttError("unknown wrap mode %r (one of %s)" % (wrap, ", ".join(MIP_WRAPS)))
     if isinstance(filter, str) and filter not in RESIZE_RULES:
         raise CvttError("unknown resize filter %r (one of %s)" % (filter, ", ".join(RESIZE_RULES)))
-    return mip_filter_value(filter) | RESIZE_KERNELS[kernel] | MIP_WRAPS[wrap]
+    return mip_filter_value(filter) | RESIZE_KERNELS[kernel] | MIP_WRAPS[wrap] | _hdr_value(hdr)
 
 
 def resize_taps(src, dst, kernel, wrap="clamp"):
@@ -467,12 +478,13 @@ def resize_taps(src, dst, kernel, wrap="clamp"):
     return first, weights
 
 
-def resize_launches(src_w, src_h, dst_w, dst_h, kernel="lanczos3", filter="box", signed=False):
+def resize_launches(src_w, src_h, dst_w, dst_h, kernel="lanczos3", filter="box", signed=False, hdr=None):
     """cvttmi_resize_launches: 1 where Context.resize of these sizes runs as one launch through LDS, 2 where it goes through an
-    intermediate in its work space"""
+    intermediate in its work space.  hdr: a name of MIP_HDR = an RGBA16F image under that range"""
     n = ctypes.c_uint32(0)
     rc = load_library().cvttmi_resize_launches(_u32(src_w, "src_w"), _u32(src_h, "src_h"), _u32(dst_w, "dst_w"), _u32(dst_h, "dst_h"),
-                                               PIXELS_RGBA8_SNORM if signed else PIXELS_RGBA8, resize_filter_word(kernel, filter), ctypes.byref(n))
+                                               PIXELS_RGBA16F if hdr is not None else PIXELS_RGBA8_SNORM if signed else PIXELS_RGBA8,
+                                               resize_filter_word(kernel, filter, hdr=hdr), ctypes.byref(n))
     if rc != 0:
         raise CvttError("cvttmi_resize_launches failed (%d)" % rc)
     return n.value
@@ -1125,7 +1137,7 @@ class Context:
         return image[None]
 
     # -- mip chains: 2x2 filter on the device, and the whole chain through one encode call --
-    def build_mips(self, image, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
+    def build_mips(self, image, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp", hdr=None):
         """(H,W,4) CUDA image -> the list of its mip levels (build_mips_array of one layer): [0] is the image itself, the others are
         (h_L, w_L, 4) views of the image's dtype into ONE allocation laid out by mip_layout.  Level L+1 is max(1, w_L >> 1) x
         max(1, h_L >> 1), a 2x2 box of the rounded level L (an odd last row / column is dropped).  uint8: (a+b+c+d+2) >> 2;
@@ -1137,17 +1149,22 @@ class Context:
         kernel: None = the 2x2 rules above; "triangle", "mitchell", "lanczos3" or "kaiser" (MIP_KERNELS) filters every level with
         that kernel's 4 / 8 / 12 taps per direction instead, under "box" (the plain rule), "srgb" or "normal", uint8 or int8
         images; an odd last row / column is then read as a neighbour.  wrap: how the taps leave the image: "clamp", "repeat" (a
-        tiling texture) or "mirror"; only with a kernel."""
-        return self.build_mips_array(self._one_layer(image), levels, signed, stream, filter, kernel, wrap)[0]
+        tiling texture) or "mirror"; only with a kernel.
+        hdr: the range of an RGBA16F image under a kernel, "nonnegative" (results clamped to [+0, 65504]) or "signed" ([-65504,
+        65504]) -- a kernel with negative lobes rings below zero in HDR data.  Such an image takes a kernel with the "box" rule and
+        a range only: the sums in float32, every product and sum rounded on its own (cvtt_mi355x.h).  None: a half image under a
+        kernel is a CvttError; a range with anything else is one too."""
+        return self.build_mips_array(self._one_layer(image), levels, signed, stream, filter, kernel, wrap, hdr)[0]
 
-    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box", kernel=None, wrap="clamp"):
+    def encode_mips(self, fmt, image, options=None, plan=None, levels=None, stream=None, mip_filter="box", kernel=None, wrap="clamp",
+                    hdr=None):
         """(H,W,4) CUDA image -> the packed blocks of every mip level: a list of (ceil(w_L/4) * ceil(h_L/4), bytes per block)
         uint8 views, level 0 first, consecutive in one allocation (container order): encode_texture of one layer.  Level L equals
         encode_image(fmt, build_mips(image)[L]) byte for byte; the levels are tiled into one block tensor and searched by ONE
         encode call (groups of eight blocks are independent), so the small levels cost no launches of their own.  fmt as for
         encode_image; "bc4s" / "bc5s" average the image as int8.  levels: None = the full chain.  mip_filter: build_mips's
-        `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L]); kernel, wrap:
-        build_mips's, and the same holds under them.
+        `filter`, under which "Level L equals ..." reads encode_image(fmt, build_mips(image, filter=mip_filter)[L]); kernel, wrap,
+        hdr: build_mips's, and the same holds under them ("bc6hu" / "bc6hs" with a kernel need hdr).
         The averaging rule follows the format, so an int8 image is taken by "bc4s" / "bc5s" alone: with any other format it is a
         CvttError (it was one for "bc7" before; the other formats used to average it as int8 and encode the bytes).
         The levels are views of the allocation that also holds the call's work space (pyramids, tiles, padded blocks: several
@@ -1158,7 +1175,7 @@ class Context:
             raise CvttError("unknown format %r" % (fmt,))
         if isinstance(image, torch.Tensor) and image.dtype == torch.int8 and texel_class(fmt) != "snorm8":
             raise CvttError("%s is not encoded from an int8 image (bc4s / bc5s are)" % fmt)
-        return self.encode_texture(fmt, self._one_layer(image), options, plan, levels, "layer", mip_filter, stream, kernel, wrap)[0]
+        return self.encode_texture(fmt, self._one_layer(image), options, plan, levels, "layer", mip_filter, stream, kernel, wrap, hdr)[0]
 
     # -- texture arrays and cube maps: `layers` images of one size through mips and encode at once (cvtt_mi355x.h) --
     def _images_in(self, images):
@@ -1187,11 +1204,11 @@ class Context:
         esz = images.element_size()
         return images, row * esz, layer * esz
 
-    def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp"):
+    def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp", hdr=None):
         """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): the mip
         chain of every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
         into one allocation: layer l's chain as mip_layout places it, texture_layout's pyramidLayerBytes apart.  levels, signed,
-        filter, kernel, wrap: as for build_mips."""
+        filter, kernel, wrap, hdr: as for build_mips."""
         import torch
         images, row_pitch, layer_pitch = self._images_in(images)
         n, h, w = (int(v) for v in images.shape[:3])
@@ -1203,7 +1220,7 @@ class Context:
         sizes = texture_layout(w, h, 4 * esz, 16, len(layout), n)
         pyramids = torch.empty(sizes.pyramidBytes, dtype=torch.uint8, device=images.device)
         self._check(self._lib.cvttmi_build_mips_array_device(self._h, pyramids.data_ptr(), sizes.pyramidBytes, images.data_ptr(), w, h, row_pitch,
-                                                             layer_pitch, kind, len(layout), n, mip_filter_word(filter, kernel, wrap),
+                                                             layer_pitch, kind, len(layout), n, mip_filter_word(filter, kernel, wrap, hdr),
                                                              ctypes.c_void_p(self._stream(stream, images.device))), "build_mips_array")
         # one strided view per level over all layers, then its n slices (pyramidLayerBytes is a multiple of 256: whole elements)
         typed = pyramids.view(images.dtype)
@@ -1212,23 +1229,31 @@ class Context:
         return [[views[l] for views in per_level] for l in range(n)]
 
     # -- resize: any size to any size on the device (cvtt_mi355x.h, "resize") --
-    def resize(self, images, width, height, kernel="lanczos3", filter="box", wrap="clamp", signed=False, out=None, stream=None):
-        """(H, W, 4) or (L, H, W, 4) CUDA tensor, uint8 or int8 -> the same rank resized to `width` x `height`
+    def resize(self, images, width, height, kernel="lanczos3", filter="box", wrap="clamp", signed=False, out=None, stream=None, hdr=None):
+        """(H, W, 4) or (L, H, W, 4) CUDA tensor, uint8 or int8 (float16 with hdr) -> the same rank resized to `width` x `height`
         (cvttmi_resize_image_device: all layers in one call).  kernel: "box" (area average), "triangle", "mitchell", "lanczos3" or
         "kaiser"; going down it is stretched by the ratio, going up it is not.  filter: "box" (the plain rule), "srgb" (colour in
         linear light, uint8 only) or "normal" (renormalised) -- build_mips's names without the "+alpha" ones; wrap: "clamp",
         "repeat" or "mirror".  int8, or signed=True: the bytes are read as int8.  At exactly half the size the result is
         build_mips(kernel=kernel)[1].  out: a CUDA tensor of the result's shape and dtype to write into (its rows and layers may be
-        strided, its texels not)."""
+        strided, its texels not).
+        hdr: "nonnegative" or "signed" (MIP_HDR) = the images are float16 (RGBA16F), resized under the "box" rule in float32 with the
+        results clamped to [+0, 65504] or [-65504, 65504] (build_mips's hdr; here it goes with every kernel, "box" included).  None: a
+        float16 image is a CvttError."""
         import torch
         single = isinstance(images, torch.Tensor) and images.dim() == 3
         images, row_pitch, layer_pitch = self._images_in(self._one_layer(images) if single else images)
-        if images.element_size() != 1:
-            raise CvttError("resize takes RGBA8 images (uint8 or int8)")
+        if hdr is None and images.element_size() != 1:
+            raise CvttError("resize takes RGBA8 images (uint8 or int8), and float16 images with hdr=")
+        if hdr is not None and images.dtype != torch.float16:
+            raise CvttError("hdr= goes with float16 images")
+        if hdr is not None and signed:
+            raise CvttError("signed selects the int8 rule of an RGBA8 image")
+        esz = images.element_size()
         n, h, w = (int(v) for v in images.shape[:3])
         width, height = _u32(width, "width"), _u32(height, "height")
-        kind = PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
-        word = resize_filter_word(kernel, filter, wrap)
+        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+        word = resize_filter_word(kernel, filter, wrap, hdr)
         shape = (n, height, width, 4)
         if out is None:
             result = torch.empty(shape, dtype=images.dtype, device=images.device)
@@ -1241,11 +1266,12 @@ class Context:
             if kept is not result:
                 raise CvttError("out must have contiguous texels, rows at least a row apart and layers at least an image apart")
         if out is None:
-            out_row, out_layer = 4 * width, 4 * width * height
+            out_row, out_layer = 4 * width * esz, 4 * width * height * esz
         need = ctypes.c_size_t(0)
         rc = self._lib.cvttmi_resize_work_bytes(w, h, width, height, kind, word, n, ctypes.byref(need))
         if rc != 0:
-            raise CvttError("resize %dx%d -> %dx%d refused: sizes and layers are 1 .. 65535; uint8 images take box, srgb and normal, int8 images box and normal" % (w, h, width, height))
+            raise CvttError("resize %dx%d -> %dx%d refused: sizes and layers are 1 .. 65535; uint8 images take box, srgb and normal, int8 images box "
+                            "and normal, float16 images box with hdr=" % (w, h, width, height))
         work = torch.empty(max(need.value, 1), dtype=torch.uint8, device=images.device)
         self._check(self._lib.cvttmi_resize_image_device(self._h, result.data_ptr(), width, height, out_row, out_layer, images.data_ptr(), w, h,
                                                          row_pitch, layer_pitch, kind, n, word, work.data_ptr(), need.value,
@@ -1255,13 +1281,13 @@ class Context:
         return out if out is not None else (result[0] if single else result)
 
     def encode_texture(self, fmt, images, options=None, plan=None, levels=None, order="layer", mip_filter="box", stream=None, kernel=None,
-                       wrap="clamp"):
+                       wrap="clamp", hdr=None):
         """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones): the layers of a texture array, or the 6 n faces of a cube (array)
         in the order +X -X +Y -Y +Z -Z -> TextureBlocks: [layer][level] packed blocks, uint8 views into ONE allocation (.base) in
         `order`: "layer" = every layer's chain consecutive (DDS), "level" = every level's layers consecutive (KTX).  One C call
         (cvttmi_encode_texture_device): the mips of all layers a launch per level, one tile launch, one search, one compact launch.
-        [l][L] equals encode_image(fmt, build_mips_array(images, ..)[l][L]) byte for byte.  fmt, levels, mip_filter, kernel, wrap: as for
-        encode_mips.  The allocation behind .base also holds the call's work space (texture_layout's workBytes, several times the
+        [l][L] equals encode_image(fmt, build_mips_array(images, ..)[l][L]) byte for byte.  fmt, levels, mip_filter, kernel, wrap, hdr:
+        as for encode_mips.  The allocation behind .base also holds the call's work space (texture_layout's workBytes, several times the
         blocks), so any view kept keeps that too: clone what is kept for long."""
         import torch
         if not has_image_form(fmt):  # (R11 reads PixelBlockScalarS16: no image form)
@@ -1284,7 +1310,7 @@ class Context:
         both = torch.empty(-(-out_bytes // 256) * 256 + sizes.workBytes, dtype=torch.uint8, device=images.device)
         out, work = both[:out_bytes].view(sizes.blocks, bpb), both[both.numel() - sizes.workBytes:]
         self._check(self._lib.cvttmi_encode_texture_device(self._h, fid, out.data_ptr(), sizes.blocks * bpb, images.data_ptr(), w, h, row_pitch,
-                                                           layer_pitch, n, levels, mip_filter_word(mip_filter, kernel, wrap), ov,
+                                                           layer_pitch, n, levels, mip_filter_word(mip_filter, kernel, wrap, hdr), ov,
                                                            ctypes.addressof(options),
                                                            ctypes.addressof(plan) if plan is not None else None, None, work.data_ptr(),
                                                            sizes.workBytes, ctypes.c_void_p(self._stream(stream, images.device))),

@@ -41,13 +41,13 @@ hipError_t cvttmi_launch_downsample_filtered(const void *d_src, size_t srcPitch,
                                              size_t dstLayer, uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t filter,
                                              hipStream_t stream);
 hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch, size_t dstLayer,
-                                  uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule, uint32_t wrap, const int16_t *taps,
-                                  uint32_t count, hipStream_t stream);
-size_t cvttmi_resize_entry_bytes(uint32_t rule);
-uint32_t cvttmi_resize_fused_rows(uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny);
+                                  uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule, uint32_t wrap, uint32_t range,
+                                  const int16_t *taps, uint32_t count, hipStream_t stream);
+size_t cvttmi_resize_entry_bytes(int kind, uint32_t rule);
+uint32_t cvttmi_resize_fused_rows(int kind, uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny);
 hipError_t cvttmi_launch_resize(const void *d_src, size_t srcPitch, size_t srcLayer, uint32_t srcW, uint32_t srcH, void *d_dst,
                                 size_t dstPitch, size_t dstLayer, uint32_t dstW, uint32_t dstH, uint32_t layers, int kind, uint32_t rule,
-                                uint32_t wrap, const int16_t *d_wx, const int32_t *d_fx, uint32_t nx, const int16_t *d_wy,
+                                uint32_t wrap, uint32_t range, const int16_t *d_wx, const int32_t *d_fx, uint32_t nx, const int16_t *d_wy,
                                 const int32_t *d_fy, uint32_t ny, void *d_mid, uint32_t fusedRows, hipStream_t stream);
 
 // decode_kernel.hip

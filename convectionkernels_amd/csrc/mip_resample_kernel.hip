@@ -1,5 +1,5 @@
 // The mip kernels wider than 2x2 (include/cvtt_mi355x.h, "mip chains", CVTTMI_MIP_KERNEL_* and CVTTMI_MIP_WRAP_*): one level per
-// launch like the other mip filters, RGBA8 and RGBA8_SNORM texels only.  An output texel reads n x n source texels (n = 4, 8 or
+// launch like the other mip filters, RGBA8 and RGBA8_SNORM texels (RGBA16F: its own kernel further down).  An output texel reads n x n source texels (n = 4, 8 or
 // 12 taps per direction, one Q14 table for every texel: tools/gen_mip_kernels.py), separably:
 //   a workgroup of 256 lanes owns a tile of kTileX x kTileY output texels.  Horizontal pass: for each of the 2 kTileY + n - 2
 //   source rows under the tile (wrapped), a lane makes four neighbouring h' from one window of n + 6 source texels -- 16-byte
@@ -201,6 +201,155 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
     }
 }
 
+// RGBA16F (resample_common.h, "RGBA16F"): the same tile, items and lanes.  The window of n + 6 texels starts at an odd column, so
+// one texel leads it from the 16-byte boundary and a 16-byte read holds two texels; an LDS entry is the four float sums (42 x 64 x
+// 16 B at most, as under SRGB, and no tables), an output texel an 8-byte store.  No scratch.
+struct MipTapsF
+{
+    float w[12];
+};
+
+template <int NTAPS>
+__global__ void __launch_bounds__(256) cvttmi_mipresample_half_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
+                                                                       uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW,
+                                                                       uint32_t srcH, uint32_t dstW, uint32_t dstH, size_t srcLayer,
+                                                                       size_t dstLayer, uint32_t wrap, uint32_t wide, uint32_t tilesY,
+                                                                       MipTapsF taps, float lo)
+{
+    constexpr int kRows = 2 * kTileY + NTAPS - 2;
+    constexpr int kWindow = NTAPS + 6;
+    constexpr int kLead = (1 - NTAPS / 2) & 1; // texels between the 16-byte boundary and the window's first texel
+    constexpr int kPairs = (kLead + kWindow + 1) / 2;
+    __shared__ float4 hbuf[kRows * kTileX];
+    src += blockIdx.z * srcLayer;
+    dst += blockIdx.z * dstLayer;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t x0 = blockIdx.x * kTileX;
+    const uint32_t groups = (min(dstW - x0, (uint32_t)kTileX) + 3u) / 4u;
+    for (uint32_t ty = blockIdx.y; ty < tilesY; ty += gridDim.y)
+    {
+        const uint32_t y0 = ty * kTileY;
+        const uint32_t tileH = min(dstH - y0, (uint32_t)kTileY);
+        const uint32_t rows = 2u * tileH + NTAPS - 2u;
+
+        // horizontal pass: item = (source row r of the tile, group g of four output columns)
+        for (uint32_t item = lane; item < rows * groups; item += 256u)
+        {
+            const uint32_t r = item / groups, g = item - r * groups;
+            const Walk wy = walkFrom(2 * (int64_t)y0 + 1 - NTAPS / 2 + (int64_t)r, srcH, wrap);
+            const uint8_t *row = src + (size_t)walkIndex(wy) * srcPitch;
+            const int64_t c0 = 2 * (int64_t)(x0 + 4u * g) + 1 - NTAPS / 2 - kLead; // even
+            uint2 texel[2 * kPairs];
+            Walk wx = walkFrom(c0, srcW, wrap);
+#pragma unroll
+            for (int q = 0; q < kPairs; q++)
+            {
+                const int64_t c = c0 + 2 * q;
+                if (wide && c >= 0 && c + 2 <= (int64_t)srcW)
+                {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(row + 8 * c);
+                    texel[2 * q] = make_uint2(v.x, v.y);
+                    texel[2 * q + 1] = make_uint2(v.z, v.w);
+                    walkStep(wx); // (inside the row the walk is at c itself, under every wrap)
+                    walkStep(wx);
+                }
+                else
+                {
+#pragma unroll
+                    for (int e = 0; e < 2; e++)
+                    {
+                        texel[2 * q + e] = reinterpret_cast<const uint2 *>(row)[walkIndex(wx)];
+                        walkStep(wx);
+                    }
+                }
+            }
+            float h[4][4];
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+            {
+                float v[kWindow];
+#pragma unroll
+                for (int i = 0; i < kWindow; i++)
+                    v[i] = halfValue((c < 2 ? texel[kLead + i].x : texel[kLead + i].y) >> (16 * (c & 1)));
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                {
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < NTAPS; k++)
+                        acc = acc + taps.w[k] * v[2 * j + k];
+                    h[j][c] = acc;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                hbuf[r * kTileX + 4u * g + j] = make_float4(h[j][0], h[j][1], h[j][2], h[j][3]);
+        }
+        __syncthreads();
+
+        // vertical pass: lane = (column x of the tile, rows 4 yg .. 4 yg + 3 of the tile)
+        const uint32_t x = lane & (kTileX - 1), yg = lane / kTileX;
+        if (x0 + x < dstW && 4u * yg < tileH)
+        {
+            float s[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    s[j][c] = 0.0f;
+#pragma unroll
+            for (int i = 0; i < kWindow; i++)
+            {
+                const float4 e = hbuf[(8u * yg + i) * kTileX + x];
+                const float ev[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (i - 2 * j >= 0 && i - 2 * j < NTAPS)
+                    {
+#pragma unroll
+                        for (int c = 0; c < 4; c++)
+                            s[j][c] = s[j][c] + taps.w[i - 2 * j] * ev[c];
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (4u * yg + j < tileH)
+                    reinterpret_cast<uint2 *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = rangedTexel(s[j], lo);
+        }
+        __syncthreads(); // the next tile's horizontal pass rewrites the entries
+    }
+}
+
+template <int NTAPS>
+hipError_t launchResampleHalf(const MipLayers &m, uint32_t wrap, const MipTapsF &taps, float lo, hipStream_t stream)
+{
+    const uint32_t dstW = m.srcW > 1u ? m.srcW >> 1 : 1u, dstH = m.srcH > 1u ? m.srcH >> 1 : 1u;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(m.src) | m.srcPitch; // 16-byte reads: as below
+    if (m.layers > 1u)
+        bits |= m.srcLayer;
+    const uint32_t wide = (bits & 15u) == 0 ? 1u : 0u;
+    const uint32_t tilesY = (dstH + kTileY - 1u) / kTileY;
+    const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers);
+    hipLaunchKernelGGL((cvttmi_mipresample_half_kernel<NTAPS>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
+                       (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, taps, lo);
+    return hipGetLastError();
+}
+
+hipError_t resampleHalfByTaps(const MipLayers &m, uint32_t wrap, const int16_t *taps, uint32_t count, uint32_t range, hipStream_t stream)
+{
+    MipTapsF t;
+    for (uint32_t k = 0; k < 12u; k++)
+        t.w[k] = k < count ? static_cast<float>(taps[k]) * (1.0f / 16384.0f) : 0.0f;
+    const float lo = hdrRangeLow(range);
+    switch (count)
+    {
+    case 4: return launchResampleHalf<4>(m, wrap, t, lo, stream);
+    case 8: return launchResampleHalf<8>(m, wrap, t, lo, stream);
+    case 12: return launchResampleHalf<12>(m, wrap, t, lo, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 template <int KIND, int RULE, int NTAPS>
 hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps, hipStream_t stream)
 {
@@ -231,26 +380,35 @@ hipError_t resampleByTaps(const MipLayers &m, uint32_t wrap, const MipTaps &taps
 }
 
 // the pairs of withKindRule; anything else is hipErrorInvalidValue
-hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, const int16_t *taps, uint32_t count, hipStream_t stream)
+// (a range goes with RGBA16F and with nothing else)
+hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, uint32_t range, const int16_t *taps, uint32_t count,
+                          hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
-    if (!taps || count > 12u || !wrapOk(wrap))
+    if (!taps || count > 12u || !wrapOk(wrap) || (kind == kRGBA16F ? !hdrRangeOk(range) : range != 0))
         return hipErrorInvalidValue;
     MipTaps t;
     for (uint32_t k = 0; k < 12u; k++)
         t.w[k] = k < count ? taps[k] : 0;
-    return withKindRule(kind, rule, [&](auto k, auto r) { return resampleByTaps<k(), r()>(m, wrap, t, count, stream); });
+    return withKindRule(kind, rule, [&](auto k, auto r) {
+        if constexpr (k() == kRGBA16F)
+            return resampleHalfByTaps(m, wrap, taps, count, range, stream);
+        else
+            return resampleByTaps<k(), r()>(m, wrap, t, count, stream);
+    });
 }
 } // namespace
 
 // One level of `layers` images (1 .. 65535, the layer in the grid's z) under a mip kernel: `rule` = CVTTMI_MIP_FILTER_BOX (the plain
-// rule), _SRGB or _NORMAL, `wrap` = 0 or one CVTTMI_MIP_WRAP_* flag, taps[0 .. count - 1] the kernel's Q14 table (count = 4, 8 or 12)
+// rule), _SRGB or _NORMAL, `wrap` = 0 or one CVTTMI_MIP_WRAP_* flag, `range` = one CVTTMI_MIP_HDR_* flag for RGBA16F and 0 otherwise,
+// taps[0 .. count - 1] the kernel's Q14 table (count = 4, 8 or 12)
 extern "C" hipError_t cvttmi_launch_resample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch, size_t dstLayer,
                                              uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, uint32_t rule, uint32_t wrap,
-                                             const int16_t *taps, uint32_t count, hipStream_t stream)
+                                             uint32_t range, const int16_t *taps, uint32_t count, hipStream_t stream)
 {
     if (!mipLayersOk(layers))
         return hipErrorInvalidValue;
-    return resampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, taps, count, stream);
+    return resampleByKind(MipLayers{d_src, srcPitch, d_dst, dstPitch, srcW, srcH, srcLayer, dstLayer, layers}, kind, rule, wrap, range, taps, count,
+                          stream);
 }

@@ -20,7 +20,9 @@ enum
     kNormal = CVTTMI_MIP_FILTER_NORMAL,
     kAlphaWeighted = CVTTMI_MIP_FILTER_ALPHA_WEIGHTED,
     kWrapRepeat = CVTTMI_MIP_WRAP_REPEAT,
-    kWrapMirror = CVTTMI_MIP_WRAP_MIRROR
+    kWrapMirror = CVTTMI_MIP_WRAP_MIRROR,
+    kHdrNonnegative = CVTTMI_MIP_HDR_NONNEGATIVE,
+    kHdrSigned = CVTTMI_MIP_HDR_SIGNED
 };
 static_assert(kRGBA8 == CVTTMI_PIXELS_RGBA8 && kRGBA16F == CVTTMI_PIXELS_RGBA16F && kRGBA8Snorm == CVTTMI_PIXELS_RGBA8_SNORM, "mip_common.h");
 
@@ -31,12 +33,15 @@ inline bool wrapOk(uint32_t wrap) // clamp or one flag
 
 // ---- the (pixel kind, rule) pairs that exist ----
 // f(kind, rule), both std::integral_constant, for the pair a call names; hipErrorInvalidValue where there is no such pair.  Under
-// a kernel and in a resize RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL.
+// a kernel and in a resize RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL, RGBA16F the plain
+// rule (in float, with a range: "RGBA16F" below; its kernels are templates of their own, so f branches on the kind).
 template <class F>
 hipError_t withKindRule(int kind, uint32_t rule, F f)
 {
     typedef std::integral_constant<int, kRGBA8> U8;
     typedef std::integral_constant<int, kRGBA8Snorm> S8;
+    if (kind == kRGBA16F && rule == kPlain)
+        return f(std::integral_constant<int, kRGBA16F>(), std::integral_constant<int, kPlain>());
     if (kind == kRGBA8 && rule == kPlain)
         return f(U8(), std::integral_constant<int, kPlain>());
     if (kind == kRGBA8 && rule == kSrgb)
@@ -197,4 +202,37 @@ __device__ __forceinline__ uint32_t normalByte(float q)
 // srgbEncode, or normalByte with the plain rule where the three sums of X are all zero -- is written out in both second passes
 // (mip_resample_kernel.hip's vertical pass, resize_kernel.hip's verticalTexel): as one function here it compiled to other
 // instructions in both, whichever way the sums were handed over (profiles/r24/finish_step.txt).
+
+// ---- RGBA16F: the plain rule in binary32, with a range (CVTTMI_MIP_HDR_*) ----
+// A texel is a uint2 of four halfs; a sum starts from +0 and takes its taps in index order, s = s + (w * v), the product and the sum
+// rounded on their own (-ffp-contract=off), w = (float)q * 2^-14 and the half as a float both exact.  An entry between the two
+// passes is the four sums, 16 bytes.  These kernels are templates of their own next to the integer ones, whose code they leave
+// as it is.
+inline bool hdrRangeOk(uint32_t range)
+{
+    return range == kHdrNonnegative || range == kHdrSigned;
+}
+
+inline float hdrRangeLow(uint32_t range) // the lower clamp; the upper one is 65504 under both
+{
+    return range == kHdrSigned ? -65504.0f : 0.0f;
+}
+
+__device__ __forceinline__ float halfValue(uint32_t bits) // of the low 16 bits
+{
+    return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(bits)));
+}
+
+// the half of a second pass's sum: clamped to [lo, 65504] by comparisons (a NaN passes both), then round-to-nearest-even with
+// subnormal halfs; a sum is never -0, a small negative one under lo = -65504 becomes 0x8000
+__device__ __forceinline__ uint32_t rangedHalf(float s, float lo)
+{
+    const float c = s < lo ? lo : (s > 65504.0f ? 65504.0f : s);
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(c));
+}
+
+__device__ __forceinline__ uint2 rangedTexel(const float (&s)[4], float lo)
+{
+    return make_uint2(rangedHalf(s[0], lo) | (rangedHalf(s[1], lo) << 16), rangedHalf(s[2], lo) | (rangedHalf(s[3], lo) << 16));
+}
 } // namespace

@@ -1,5 +1,6 @@
 // Resize to any size (include/cvtt_mi355x.h, "resize"): the Q14 two-pass rule of the mip kernels with one weight row per output
-// column and per output row.  RGBA8 and RGBA8_SNORM texels; the plain rule, SRGB and NORMAL; clamp, repeat and mirror.  The tables
+// column and per output row.  RGBA8 and RGBA8_SNORM texels; the plain rule, SRGB and NORMAL; clamp, repeat and mirror.  (RGBA16F:
+// the plain rule in float, kernels of its own further down, the same routes, tables and work space.)  The tables
 // (cvttmi_resize_taps: weights and first taps of both axes) lie in device memory, in the caller's work space:
 //   wx[k * dstW + x]  the weight of tap k of output column x (tap-major: the lanes of a wave read neighbouring columns)
 //   fx[x]             the unwrapped source column of its tap 0
@@ -268,6 +269,130 @@ __global__ void __launch_bounds__(256) cvttmi_resize_v_kernel(ResizeArgs a)
     }
 }
 
+// ---- RGBA16F (resample_common.h, "RGBA16F"): the same two routes, an entry the four float sums, 8-byte reads and stores ----
+__device__ __forceinline__ float4 horizontalHalf(const ResizeArgs &a, const uint2 *row, int32_t first, const int16_t *tap, uint32_t stride)
+{
+    Walk w = walkFrom(first, a.srcW, a.wrap);
+    float h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t k = 0; k < a.nx; k++, tap += stride)
+    {
+        const uint2 texel = row[walkIndex(w)];
+        walkStep(w);
+        const float q = static_cast<float>(*tap) * (1.0f / 16384.0f);
+        h[0] = h[0] + q * halfValue(texel.x);
+        h[1] = h[1] + q * halfValue(texel.x >> 16);
+        h[2] = h[2] + q * halfValue(texel.y);
+        h[3] = h[3] + q * halfValue(texel.y >> 16);
+    }
+    return make_float4(h[0], h[1], h[2], h[3]);
+}
+
+template <class At>
+__device__ __forceinline__ uint2 verticalHalf(const int16_t *tap, uint32_t ny, float lo, At at)
+{
+    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t k = 0; k < ny; k++)
+    {
+        const float q = static_cast<float>(tap[k]) * (1.0f / 16384.0f);
+        const float4 e = at(k);
+        s[0] = s[0] + q * e.x;
+        s[1] = s[1] + q * e.y;
+        s[2] = s[2] + q * e.z;
+        s[3] = s[3] + q * e.w;
+    }
+    return rangedTexel(s, lo);
+}
+
+__global__ void __launch_bounds__(256) cvttmi_resize_half_fused_kernel(ResizeArgs a, uint32_t rows, float lo)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    float4 *hbuf = reinterpret_cast<float4 *>(lds); // rows x kTileX entries
+    const uint32_t lane = threadIdx.x, x = lane & (kTileX - 1), x0 = blockIdx.x * kTileX, y0 = blockIdx.y * kTileY;
+    const uint32_t tileH = min(a.dstH - y0, (uint32_t)kTileY);
+    const bool inside = x0 + x < a.dstW;
+    const int32_t top = a.fy[y0];
+    const uint32_t used = static_cast<uint32_t>(a.fy[y0 + tileH - 1] - top) + a.ny; // <= rows: the host has looked at every tile
+    if (inside && used <= rows)
+    {
+        const int32_t first = a.fx[x0 + x];
+        const int16_t *tap = a.wx + x0 + x;
+        Walk wy = walkFrom((int64_t)top + (lane / kTileX), a.srcH, a.wrap);
+        for (uint32_t r = lane / kTileX; r < used; r += 256u / kTileX)
+        {
+            const uint2 *row = reinterpret_cast<const uint2 *>(a.src + blockIdx.z * a.srcLayer + (size_t)walkIndex(wy) * a.srcPitch);
+            hbuf[r * kTileX + x] = horizontalHalf(a, row, first, tap, a.dstW);
+#pragma unroll
+            for (uint32_t i = 0; i < 256u / kTileX; i++)
+                walkStep(wy);
+        }
+    }
+    __syncthreads();
+    if (inside && used <= rows)
+    {
+        const uint32_t yg = lane / kTileX;
+        for (uint32_t j = 0; j < (uint32_t)kTileY / (256u / kTileX); j++)
+        {
+            const uint32_t y = y0 + yg * (kTileY / (256u / kTileX)) + j;
+            if (y >= y0 + tileH)
+                break;
+            const float4 *column = hbuf + static_cast<uint32_t>(a.fy[y] - top) * kTileX + x;
+            const uint2 out = verticalHalf(a.wy + (size_t)y * a.ny, a.ny, lo, [&](uint32_t k) { return column[k * kTileX]; });
+            reinterpret_cast<uint2 *>(a.dst + blockIdx.z * a.dstLayer + (size_t)y * a.dstPitch)[x0 + x] = out;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) cvttmi_resize_half_h_kernel(ResizeArgs a)
+{
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.dstW)
+        return;
+    const int32_t first = a.fx[x];
+    const uint32_t r0 = blockIdx.y * kRows, r1 = min(r0 + kRows, a.srcH);
+    float4 *mid = static_cast<float4 *>(a.mid) + ((size_t)blockIdx.z * a.srcH + r0) * a.dstW + x;
+    for (uint32_t r = r0; r < r1; r++, mid += a.dstW)
+    {
+        const uint2 *row = reinterpret_cast<const uint2 *>(a.src + blockIdx.z * a.srcLayer + (size_t)r * a.srcPitch);
+        *mid = horizontalHalf(a, row, first, a.wx + x, a.dstW);
+    }
+}
+
+__global__ void __launch_bounds__(256) cvttmi_resize_half_v_kernel(ResizeArgs a, float lo)
+{
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.dstW)
+        return;
+    const float4 *mid = static_cast<const float4 *>(a.mid) + (size_t)blockIdx.z * a.srcH * a.dstW + x;
+    const uint32_t y0 = blockIdx.y * kRows, y1 = min(y0 + kRows, a.dstH);
+    for (uint32_t y = y0; y < y1; y++)
+    {
+        Walk w = walkFrom(a.fy[y], a.srcH, a.wrap);
+        const uint2 out = verticalHalf(a.wy + (size_t)y * a.ny, a.ny, lo, [&](uint32_t) {
+            const float4 e = mid[(size_t)walkIndex(w) * a.dstW];
+            walkStep(w);
+            return e;
+        });
+        reinterpret_cast<uint2 *>(a.dst + blockIdx.z * a.dstLayer + (size_t)y * a.dstPitch)[x] = out;
+    }
+}
+
+hipError_t launchResizeHalf(const ResizeArgs &a, uint32_t layers, uint32_t fusedRows, float lo, hipStream_t stream)
+{
+    if (fusedRows)
+    {
+        const dim3 grid((a.dstW + kTileX - 1u) / kTileX, (a.dstH + kTileY - 1u) / kTileY, layers);
+        hipLaunchKernelGGL(cvttmi_resize_half_fused_kernel, grid, dim3(256), (size_t)fusedRows * kTileX * sizeof(float4), stream, a, fusedRows, lo);
+        return hipGetLastError();
+    }
+    const uint32_t gx = (a.dstW + 255u) / 256u;
+    hipLaunchKernelGGL(cvttmi_resize_half_h_kernel, dim3(gx, (a.srcH + kRows - 1u) / kRows, layers), dim3(256), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(cvttmi_resize_half_v_kernel, dim3(gx, (a.dstH + kRows - 1u) / kRows, layers), dim3(256), 0, stream, a, lo);
+    return hipGetLastError();
+}
+
 template <int KIND, int RULE>
 hipError_t launchResize(const ResizeArgs &a, uint32_t layers, uint32_t fusedRows, hipStream_t stream)
 {
@@ -288,17 +413,19 @@ hipError_t launchResize(const ResizeArgs &a, uint32_t layers, uint32_t fusedRows
 }
 } // namespace
 
-// bytes of one entry of the intermediate under a rule (0: no such rule)
-extern "C" size_t cvttmi_resize_entry_bytes(uint32_t rule)
+// bytes of one entry of the intermediate of a pixel kind under a rule (0: no such pair)
+extern "C" size_t cvttmi_resize_entry_bytes(int kind, uint32_t rule)
 {
+    if (kind == kRGBA16F)
+        return rule == kPlain ? sizeof(float4) : 0;
     return rule == kPlain ? sizeof(EntryOf<kPlain>::type) : rule == kSrgb ? sizeof(EntryOf<kSrgb>::type) : rule == kNormal ? sizeof(EntryOf<kNormal>::type) : 0;
 }
 
 // The path of a resize, from the first taps of its dstH output rows (ny taps each): the most source rows under one tile where
 // they fit in kFusedLdsBytes of LDS next to the sRGB tables -- one launch --, else 0 -- two launches.  Host only.
-extern "C" uint32_t cvttmi_resize_fused_rows(uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny)
+extern "C" uint32_t cvttmi_resize_fused_rows(int kind, uint32_t rule, const int32_t *first, uint32_t dstH, uint32_t ny)
 {
-    const size_t entry = cvttmi_resize_entry_bytes(rule);
+    const size_t entry = cvttmi_resize_entry_bytes(kind, rule);
     const size_t room = kFusedLdsBytes - (rule == kSrgb ? sizeof(SrgbEncodeTables) + 512u : 0u);
     uint64_t rows = 0;
     for (uint32_t y0 = 0; y0 < dstH; y0 += kTileY)
@@ -313,18 +440,23 @@ extern "C" uint32_t cvttmi_resize_fused_rows(uint32_t rule, const int32_t *first
 // `layers` images (1 .. 65535, sizes 1 .. 65535) resized under `rule` = CVTTMI_MIP_FILTER_BOX (the plain rule), _SRGB or _NORMAL and
 // `wrap` = 0 or one CVTTMI_MIP_WRAP_* flag.  d_wx (tap-major), d_fx, d_wy (row-major), d_fy: the tables, in device memory.
 // fusedRows = cvttmi_resize_fused_rows of d_fy's values; where it is 0, d_mid holds layers x srcH x dstW entries of
-// cvttmi_resize_entry_bytes(rule), on a 16-byte boundary.
+// cvttmi_resize_entry_bytes(kind, rule), on a 16-byte boundary.  `range`: one CVTTMI_MIP_HDR_* flag for RGBA16F, 0 otherwise.
 extern "C" hipError_t cvttmi_launch_resize(const void *d_src, size_t srcPitch, size_t srcLayer, uint32_t srcW, uint32_t srcH, void *d_dst,
                                            size_t dstPitch, size_t dstLayer, uint32_t dstW, uint32_t dstH, uint32_t layers, int kind,
-                                           uint32_t rule, uint32_t wrap, const int16_t *d_wx, const int32_t *d_fx, uint32_t nx,
+                                           uint32_t rule, uint32_t wrap, uint32_t range, const int16_t *d_wx, const int32_t *d_fx, uint32_t nx,
                                            const int16_t *d_wy, const int32_t *d_fy, uint32_t ny, void *d_mid, uint32_t fusedRows,
                                            hipStream_t stream)
 {
     if (!mipLayersOk(layers) || srcW == 0 || srcH == 0 || dstW == 0 || dstH == 0 || (srcW | srcH | dstW | dstH) > 65535u || nx == 0 || ny == 0 ||
         !wrapOk(wrap) || !d_wx || !d_fx || !d_wy || !d_fy || (!fusedRows && !d_mid) ||
-        (size_t)fusedRows * kTileX * cvttmi_resize_entry_bytes(rule) > kFusedLdsBytes)
+        (size_t)fusedRows * kTileX * cvttmi_resize_entry_bytes(kind, rule) > kFusedLdsBytes || (kind == kRGBA16F ? !hdrRangeOk(range) : range != 0))
         return hipErrorInvalidValue;
     const ResizeArgs a = {static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_dst), d_mid, srcPitch, srcLayer, dstPitch, dstLayer,
                           srcW, srcH, dstW, dstH, d_wx, d_wy, d_fx, d_fy, nx, ny, wrap};
-    return withKindRule(kind, rule, [&](auto k, auto r) { return launchResize<k(), r()>(a, layers, fusedRows, stream); });
+    return withKindRule(kind, rule, [&](auto k, auto r) {
+        if constexpr (k() == kRGBA16F)
+            return launchResizeHalf(a, layers, fusedRows, hdrRangeLow(range), stream);
+        else
+            return launchResize<k(), r()>(a, layers, fusedRows, stream);
+    });
 }

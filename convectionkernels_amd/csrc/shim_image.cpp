@@ -18,24 +18,31 @@ namespace
         return (pixelFormat == CVTTMI_PIXELS_RGBA8 || pixelFormat == CVTTMI_PIXELS_RGBA8_SNORM) ? 4u : pixelFormat == CVTTMI_PIXELS_RGBA16F ? 8u : 0u;
     }
     // the filters a pixel kind takes (cvtt_mi355x.h, CVTTMI_MIP_FILTER_*, CVTTMI_MIP_KERNEL_*, CVTTMI_MIP_WRAP_*)
-    // A filter word's three fields: `rule` is everything outside the other two (BOX, SRGB or NORMAL, ALPHA_WEIGHTED with them, and any
-    // bit that means nothing), `code` the kernel (0 = none), `wrap` the wrap flags as they stand in the word.
+    // A filter word's four fields: `rule` is everything outside the other three (BOX, SRGB or NORMAL, ALPHA_WEIGHTED with them, and
+    // any bit that means nothing), `code` the kernel (0 = none), `wrap` the wrap flags and `range` the CVTTMI_MIP_HDR_* flags as they
+    // stand in the word.
     struct FilterWord
     {
-        uint32_t rule, code, wrap;
+        uint32_t rule, code, wrap, range;
     };
     FilterWord splitFilter(uint32_t filter)
     {
         const uint32_t kernel = 0xf0u, wrap = CVTTMI_MIP_WRAP_REPEAT | CVTTMI_MIP_WRAP_MIRROR;
-        return FilterWord{filter & ~(kernel | wrap), (filter & kernel) >> 4, filter & wrap};
+        const uint32_t range = CVTTMI_MIP_HDR_NONNEGATIVE | CVTTMI_MIP_HDR_SIGNED;
+        return FilterWord{filter & ~(kernel | wrap | range), (filter & kernel) >> 4, filter & wrap, filter & range};
     }
     bool oneWrapAtMost(uint32_t wrap)
     {
         return wrap != (CVTTMI_MIP_WRAP_REPEAT | CVTTMI_MIP_WRAP_MIRROR);
     }
-    // does the pixel kind take the rule under a kernel (in a mip chain or a resize)?  No ALPHA_WEIGHTED there, and no RGBA16F.
-    bool kernelRuleFits(int pixelFormat, uint32_t rule)
+    // does the pixel kind take the rule and the range under a kernel (in a mip chain or a resize)?  No ALPHA_WEIGHTED there; RGBA16F
+    // takes the plain rule with exactly one range flag, and a range flag goes with nothing else.
+    bool kernelRuleFits(int pixelFormat, uint32_t rule, uint32_t range)
     {
+        if (pixelFormat == CVTTMI_PIXELS_RGBA16F)
+            return rule == CVTTMI_MIP_FILTER_BOX && (range == CVTTMI_MIP_HDR_NONNEGATIVE || range == CVTTMI_MIP_HDR_SIGNED);
+        if (range != 0)
+            return false;
         if (pixelFormat == CVTTMI_PIXELS_RGBA8)
             return rule == CVTTMI_MIP_FILTER_BOX || rule == CVTTMI_MIP_FILTER_SRGB || rule == CVTTMI_MIP_FILTER_NORMAL;
         return pixelFormat == CVTTMI_PIXELS_RGBA8_SNORM && (rule == CVTTMI_MIP_FILTER_BOX || rule == CVTTMI_MIP_FILTER_NORMAL);
@@ -53,7 +60,9 @@ namespace
         const FilterWord f = splitFilter(filter);
         uint32_t count;
         if (f.code || f.wrap) // a kernel; a wrap flag alone is nothing
-            return mipKernelTaps(f.code, &count) && oneWrapAtMost(f.wrap) && kernelRuleFits(pixelFormat, f.rule);
+            return mipKernelTaps(f.code, &count) && oneWrapAtMost(f.wrap) && kernelRuleFits(pixelFormat, f.rule, f.range);
+        if (f.range) // a range flag without a kernel: the 2x2 rules have no range
+            return false;
         if (f.rule == CVTTMI_MIP_FILTER_BOX)
             return true;
         if (f.rule == CVTTMI_MIP_FILTER_NORMAL)
@@ -63,7 +72,8 @@ namespace
     }
     const char *const kMipFilterText =
         "mip filter: RGBA8 takes BOX, SRGB, either with ALPHA_WEIGHTED, and NORMAL; RGBA8_SNORM BOX and NORMAL; RGBA16F BOX; a "
-        "CVTTMI_MIP_KERNEL_* goes with BOX, SRGB or NORMAL of RGBA8 / RGBA8_SNORM, and one CVTTMI_MIP_WRAP_* flag only with a kernel";
+        "CVTTMI_MIP_KERNEL_* goes with BOX, SRGB or NORMAL of RGBA8 / RGBA8_SNORM and with BOX of RGBA16F, which then needs exactly one "
+        "CVTTMI_MIP_HDR_* flag (a flag goes with nothing else); one CVTTMI_MIP_WRAP_* flag only with a kernel";
 }
 
 extern "C"
@@ -207,7 +217,7 @@ extern "C"
                 uint8_t *dst = d_pyramids + (size_t)first * pyramidLayerBytes + table[l].byteOffset;
                 const hipError_t e =
                     taps ? cvttmi_launch_resample(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes, table[l - 1].width,
-                                                  table[l - 1].height, n, pixelFormat, f.rule, f.wrap, taps, tapCount, stream)
+                                                  table[l - 1].height, n, pixelFormat, f.rule, f.wrap, f.range, taps, tapCount, stream)
                     : f.rule == CVTTMI_MIP_FILTER_BOX
                         ? cvttmi_launch_downsample(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes, table[l - 1].width,
                                                    table[l - 1].height, n, pixelFormat, stream)
@@ -490,10 +500,11 @@ extern "C"
             return code <= CVTT_MIP_KERNELS ? r2[code] : 0;
         }
         // the filter word of the resize calls: rule (one that RGBA8, which takes them all, takes) | kernel (0 = box) | at most one wrap
-        // flag; false = not such a word
+        // flag, or the word of RGBA16F: the plain rule | kernel | wrap | one range flag; false = not such a word
         bool resizeFilterOk(const FilterWord &f)
         {
-            return resizeRadius2(f.code) != 0 && oneWrapAtMost(f.wrap) && kernelRuleFits(CVTTMI_PIXELS_RGBA8, f.rule);
+            return resizeRadius2(f.code) != 0 && oneWrapAtMost(f.wrap) &&
+                   kernelRuleFits(f.range ? CVTTMI_PIXELS_RGBA16F : CVTTMI_PIXELS_RGBA8, f.rule, f.range);
         }
         uint32_t resizeTapCount(uint32_t src, uint32_t dst, uint32_t code)
         {
@@ -607,7 +618,8 @@ extern "C"
         };
         const char *const kResizeFilterText =
             "resize filter: the plain rule, SRGB or NORMAL (RGBA8_SNORM: not SRGB) | kernel 0 (box) or a CVTTMI_MIP_KERNEL_* | at most one "
-            "CVTTMI_MIP_WRAP_* flag; RGBA8 or RGBA8_SNORM texels";
+            "CVTTMI_MIP_WRAP_* flag; RGBA8 or RGBA8_SNORM texels, or RGBA16F texels with the plain rule and exactly one CVTTMI_MIP_HDR_* flag "
+            "(a flag goes with nothing else)";
         // NULL = fine, else what is wrong
         const char *resizePlan(uint32_t srcW, uint32_t srcH, uint32_t dstW, uint32_t dstH, int pixelFormat, uint32_t filter, uint32_t layers,
                                ResizePlan *plan)
@@ -616,7 +628,7 @@ extern "C"
                 return "resize: sizes and layers are 1 .. 65535";
             ResizePlan p;
             p.f = splitFilter(filter);
-            if (!resizeFilterOk(p.f) || !kernelRuleFits(pixelFormat, p.f.rule))
+            if (!resizeFilterOk(p.f) || !kernelRuleFits(pixelFormat, p.f.rule, p.f.range))
                 return kResizeFilterText;
             const uint32_t code = p.f.code, rule = p.f.rule;
             p.nx = resizeTapCount(srcW, dstW, code);
@@ -629,8 +641,8 @@ extern "C"
             std::vector<int32_t> first(dstH);
             for (uint32_t y = 0; y < dstH; y++)
                 first[y] = resizeFirst(srcH, dstH, code, y);
-            p.fusedRows = cvttmi_resize_fused_rows(rule, first.data(), dstH, p.ny);
-            p.workBytes = p.tableBytes + (p.fusedRows ? 0 : (size_t)layers * srcH * dstW * cvttmi_resize_entry_bytes(rule)); // (below 2^52)
+            p.fusedRows = cvttmi_resize_fused_rows(pixelFormat, rule, first.data(), dstH, p.ny);
+            p.workBytes = p.tableBytes + (p.fusedRows ? 0 : (size_t)layers * srcH * dstW * cvttmi_resize_entry_bytes(pixelFormat, rule)); // (below 2^52)
             *plan = p;
             return NULL;
         }
@@ -677,15 +689,16 @@ extern "C"
             return fail(ctx, CVTTMI_E_INVALID, wrong);
         if (!d_work)
             return fail(ctx, CVTTMI_E_INVALID, "invalid argument");
-        if (const char *wrong = textureImagesWrong(d_src, srcW, srcH, srcRowPitchBytes, srcLayerPitchBytes, 4, layers))
+        const size_t texel = mipTexelBytes(pixelFormat); // (the plan has passed the kind)
+        if (const char *wrong = textureImagesWrong(d_src, srcW, srcH, srcRowPitchBytes, srcLayerPitchBytes, texel, layers))
             return fail(ctx, CVTTMI_E_INVALID, wrong);
-        if (const char *wrong = textureImagesWrong(d_dst, dstW, dstH, dstRowPitchBytes, dstLayerPitchBytes, 4, layers))
+        if (const char *wrong = textureImagesWrong(d_dst, dstW, dstH, dstRowPitchBytes, dstLayerPitchBytes, texel, layers))
             return fail(ctx, CVTTMI_E_INVALID, wrong);
         if (workBytes < plan.workBytes)
             return fail(ctx, CVTTMI_E_INVALID, "work space smaller than cvttmi_resize_work_bytes asks for");
-        if (!alignedTo(d_src, 4) || !alignedTo(d_dst, 4) || (reinterpret_cast<uintptr_t>(d_work) & 255u) != 0)
+        if (!alignedTo(d_src, texel) || !alignedTo(d_dst, texel) || (reinterpret_cast<uintptr_t>(d_work) & 255u) != 0)
             return fail(ctx, CVTTMI_E_INVALID, kMisaligned);
-        const uint32_t code = plan.f.code, tablesOf = filter & ~plan.f.wrap; // (the tables do not depend on the wrap)
+        const uint32_t code = plan.f.code, tablesOf = filter & ~(plan.f.wrap | plan.f.range); // (the tables depend on neither the wrap nor the range)
         hipStream_t stream = static_cast<hipStream_t>(hipStream);
         return withDevice(ctx, [&] {
             // the slot that holds these tables already, or the next of the ring
@@ -741,7 +754,7 @@ extern "C"
                 if (!slot->inFlight)
                     (void)hipStreamSynchronize(stream); // (no event to wait for later: the copy ends here)
                 e2 = cvttmi_launch_resize(d_src, srcRowPitchBytes, srcLayerPitchBytes, srcW, srcH, d_dst, dstRowPitchBytes, dstLayerPitchBytes, dstW,
-                                          dstH, layers, pixelFormat, plan.f.rule, plan.f.wrap, reinterpret_cast<const int16_t *>(work + plan.wx),
+                                          dstH, layers, pixelFormat, plan.f.rule, plan.f.wrap, plan.f.range, reinterpret_cast<const int16_t *>(work + plan.wx),
                                           reinterpret_cast<const int32_t *>(work + plan.fx), plan.nx, reinterpret_cast<const int16_t *>(work + plan.wy),
                                           reinterpret_cast<const int32_t *>(work + plan.fy), plan.ny, work + plan.tableBytes, plan.fusedRows, stream);
                 return e2 == hipSuccess ? CVTTMI_OK : fail(ctx, CVTTMI_E_HIP, "resize kernel launch", e2);

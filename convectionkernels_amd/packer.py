@@ -7,6 +7,10 @@ The command line follows the reference's example packer (etc2packer.cpp:44-105: 
 file, `-quality 1..100` for a BC7 plan).  The image is uploaded once; tiling into groups of eight 4x4 blocks with
 edge clamping (etc2packer.cpp:215-248), encoding and the removal of padding blocks all run on the device, and the
 packed blocks are already in container order.  The input is anything PIL opens, or a .npy of shape (H, W, 4) uint8.
+-format bc6hu|bc6hs: the input is a .npy of shape (H, W, 4) -- (L, H, W, 4) with -array / -cube --, float16, or float32, which is
+clamped to +-65504 and rounded to nearest even; non-finite values and every other input are refused.  Under -mipkernel and the
+resize flags such an image is filtered in float32 and the results are clamped to the format's range (Context.build_mips's hdr):
+bc6hu "nonnegative" [+0, 65504], bc6hs "signed" [-65504, 65504].  With -metrics BC6H prints the MSE; it has no PSNR (nan).
 -metrics: after the file is written, print the encoding error to stdout, measured on the device against the input image
 (Context.measure_image: one line per measured channel with its MSE and PSNR, then the PSNR over all of them; R11 has no
 image form and is measured over the written blocks against their tiles, the clamped texels of the edge blocks included).
@@ -17,7 +21,7 @@ R11, which has no image form.
 -mipfilter box|srgb|normal, -alphaweight: the filter of the chain (Context.build_mips: "srgb" averages colour in linear light,
 "normal" renormalises a normal map, -alphaweight weights colour by alpha -- with box or srgb); either implies -mips.
 -mipkernel triangle|mitchell|lanczos3|kaiser: every level is filtered with that kernel (4, 8 or 12 taps per direction) instead of the
-2x2 rule, under -mipfilter box (the default), srgb or normal; implies -mips.  Not with -alphaweight, not for bc6h.  -wrap
+2x2 rule, under -mipfilter box (the default), srgb or normal; implies -mips.  Not with -alphaweight; bc6h: box only.  -wrap
 clamp|repeat|mirror: how the kernel's taps leave the image (repeat: a tiling texture); only with -mipkernel.
 -srgb: the file carries the sRGB code of its format (container.SRGB_FORMATS).  Only a mark: level 0 and the encode are unchanged.
 -array: every input is one layer of a texture array (N inputs, then the output); -cube: the inputs are the faces of a cube in the
@@ -30,7 +34,8 @@ the device (Context.resize) before anything else; -mips, -metrics and the contai
 side becomes at most N, the aspect kept, each side max(1, floor(side * N / larger + 0.5)); never enlarges.  -pow2: each side on its own
 to the next power of two up, down, or the nearer of the two (the larger one from the middle on).  -resizekernel (default lanczos3; box is
 an area average), -resizerule box|srgb|normal (default box: the plain rule) and -resizewrap (default clamp) say how, and go only with
-one of the three.  Sizes are 1 .. 65535.  Not for bc6hu / bc6hs."""
+one of the three.  Sizes are 1 .. 65535.  bc6hu / bc6hs: -resizerule box only.  -mipfilter srgb|normal and -alphaweight are not for
+bc6hu / bc6hs either."""
 import re
 import sys
 
@@ -49,6 +54,25 @@ def load_rgba8(path):
         img = np.array(Image.open(path).convert("RGBA"))
     if img.ndim != 3 or img.shape[2] != 4 or img.dtype != np.uint8:
         raise ValueError("expected an (H, W, 4) uint8 image, got %s %s" % (img.shape, img.dtype))
+    return np.ascontiguousarray(img)
+
+
+HALF_FORMATS = {"bc6hu": "nonnegative", "bc6hs": "signed"}  # the formats encoded from RGBA16F images, and their range (api.MIP_HDR)
+
+
+def load_rgba16f(path, fmt, ndim=3):
+    """the image of a half-float format: a .npy of `ndim` dimensions, float16 or float32 -> float16; anything else is a ValueError that
+    names the format"""
+    shape = "(H, W, 4)" if ndim == 3 else "(L, H, W, 4)"
+    if not path.endswith(".npy"):
+        raise ValueError("%s is encoded from a float16 or float32 .npy of shape %s, got %s" % (fmt, shape, path))
+    img = np.load(path)
+    if img.ndim != ndim or img.shape[-1] != 4 or 0 in img.shape or img.dtype not in (np.float16, np.float32):
+        raise ValueError("%s is encoded from a float16 or float32 .npy of shape %s, got %s %s" % (fmt, shape, img.shape, img.dtype))
+    if not np.isfinite(img).all():
+        raise ValueError("%s: the image holds non-finite values (NaN or infinity)" % fmt)
+    if img.dtype == np.float32:
+        img = np.clip(img, np.float32(-65504.0), np.float32(65504.0)).astype(np.float16)  # (astype rounds to nearest even)
     return np.ascontiguousarray(img)
 
 
@@ -82,23 +106,23 @@ def encode_file(image, fmt, options=None, plan=None, ctx=None):
     return packed.cpu().numpy()
 
 
-def encode_file_mips(image, fmt, options=None, plan=None, ctx=None, mip_filter="box", kernel=None, wrap="clamp"):
-    """(H, W, 4) uint8 numpy image -> [packed blocks of level L], the full chain, container order (not R11)"""
+def encode_file_mips(image, fmt, options=None, plan=None, ctx=None, mip_filter="box", kernel=None, wrap="clamp", hdr=None):
+    """(H, W, 4) uint8 (BC6H: float16) numpy image -> [packed blocks of level L], the full chain, container order (not R11)"""
     import torch
     ctx = ctx or api.default_context()
     levels = ctx.encode_mips(container.canonical(fmt), torch.from_numpy(image).cuda(ctx.device), options, plan, mip_filter=mip_filter,
-                             kernel=kernel, wrap=wrap)
+                             kernel=kernel, wrap=wrap, hdr=hdr)
     torch.cuda.synchronize(ctx.device)
     return [level.cpu().numpy() for level in levels]
 
 
-def measure_file_mips(image, fmt, levels, ctx=None, mip_filter="box", kernel=None, wrap="clamp"):
+def measure_file_mips(image, fmt, levels, ctx=None, mip_filter="box", kernel=None, wrap="clamp", hdr=None):
     """[ErrorReport of level L against its own image] for the levels encode_file_mips returned, level 0 left out"""
     import torch
     ctx = ctx or api.default_context()
     fmt = container.canonical(fmt)
     images = ctx.build_mips(torch.from_numpy(np.ascontiguousarray(image)).cuda(ctx.device), len(levels), signed=fmt in ("bc4s", "bc5s"),
-                            filter=mip_filter, kernel=kernel, wrap=wrap)
+                            filter=mip_filter, kernel=kernel, wrap=wrap, hdr=hdr)
     return [ctx.measure_image(fmt, img, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
             for img, packed in zip(images[1:], levels[1:])]
 
@@ -126,15 +150,22 @@ def measure_file(image, fmt, packed, options=None, ctx=None):
     return ctx.measure_image(fmt, dev, torch.from_numpy(np.ascontiguousarray(packed)).cuda(ctx.device))
 
 
-def load_layers(paths):
-    """the inputs of -array / -cube -> (L, H, W, 4) uint8: one image per path, or a single .npy of that shape"""
-    if len(paths) == 1 and paths[0].endswith(".npy"):
+def load_layers(paths, fmt=None):
+    """the inputs of -array / -cube -> (L, H, W, 4) uint8 (a format of HALF_FORMATS: float16): one image per path, or a single .npy of
+    that shape"""
+    if fmt in HALF_FORMATS:
+        if len(paths) == 1 and paths[0].endswith(".npy") and np.load(paths[0], mmap_mode="r").ndim == 4:
+            return load_rgba16f(paths[0], fmt, 4)
+        images = [load_rgba16f(p, fmt) for p in paths]
+    elif len(paths) == 1 and paths[0].endswith(".npy"):
         stack = np.load(paths[0])
         if stack.ndim == 4:
             if stack.shape[0] < 1 or stack.shape[3] != 4 or stack.dtype != np.uint8:
                 raise ValueError("expected an (L, H, W, 4) uint8 array, got %s %s" % (stack.shape, stack.dtype))
             return np.ascontiguousarray(stack)
-    images = [load_rgba8(p) for p in paths]
+        images = [load_rgba8(p) for p in paths]
+    else:
+        images = [load_rgba8(p) for p in paths]
     for p, img in zip(paths, images):
         if img.shape != images[0].shape:
             raise ValueError("all layers must be of one size: %s is %dx%d, %s is %dx%d"
@@ -143,12 +174,12 @@ def load_layers(paths):
 
 
 def encode_file_texture(images, fmt, options=None, plan=None, ctx=None, mips=False, mip_filter="box", order="level", kernel=None,
-                        wrap="clamp"):
-    """(L, H, W, 4) uint8 numpy layers -> [layer][level] packed blocks (numpy), one level or the full chain (not R11)"""
+                        wrap="clamp", hdr=None):
+    """(L, H, W, 4) uint8 (BC6H: float16) numpy layers -> [layer][level] packed blocks (numpy), one level or the full chain (not R11)"""
     import torch
     ctx = ctx or api.default_context()
     blocks = ctx.encode_texture(container.canonical(fmt), torch.from_numpy(images).cuda(ctx.device), options, plan,
-                                levels=None if mips else 1, order=order, mip_filter=mip_filter, kernel=kernel, wrap=wrap)
+                                levels=None if mips else 1, order=order, mip_filter=mip_filter, kernel=kernel, wrap=wrap, hdr=hdr)
     torch.cuda.synchronize(ctx.device)
     host, start = blocks.base.cpu().numpy(), blocks.base.data_ptr()
     per = host.shape[1]
@@ -177,12 +208,13 @@ def resized_size(w, h, resize=None, maxsize=None, pow2=None):
     return w, h
 
 
-def resize_file(images, width, height, kernel="lanczos3", rule="box", wrap="clamp", signed=False, ctx=None):
-    """(H, W, 4) or (L, H, W, 4) uint8 numpy image(s) -> the same resized to width x height on the device (all layers in one call)"""
+def resize_file(images, width, height, kernel="lanczos3", rule="box", wrap="clamp", signed=False, ctx=None, hdr=None):
+    """(H, W, 4) or (L, H, W, 4) uint8 numpy image(s) -> the same resized to width x height on the device (all layers in one call);
+    float16 images with hdr, their range (api.MIP_HDR)"""
     import torch
     ctx = ctx or api.default_context()
     out = ctx.resize(torch.from_numpy(np.ascontiguousarray(images)).cuda(ctx.device), width, height, kernel=kernel, filter=rule, wrap=wrap,
-                     signed=signed)
+                     signed=signed, hdr=hdr)
     torch.cuda.synchronize(ctx.device)
     return out.cpu().numpy()
 
@@ -283,8 +315,9 @@ def main(argv=None):
             raise ValueError("-alphaweight goes with -mipfilter box or srgb")
         if mip_kernel is not None and alpha_weight:
             raise ValueError("-mipkernel does not go with -alphaweight")
-        if mip_kernel is not None and fmt in ("bc6hu", "bc6hs"):
-            raise ValueError("-mipkernel: %s is encoded from half-float images, which take the 2x2 rule only" % fmt)
+        if fmt in HALF_FORMATS and (mip_filter != "box" or resize_rule not in (None, "box")):
+            raise ValueError("%s is encoded from half-float images, which take the box rule only (no -mipfilter srgb|normal, -alphaweight, "
+                             "-resizerule srgb|normal)" % fmt)
         if wrap is not None and mip_kernel is None:
             raise ValueError("-wrap goes with -mipkernel")
         if fmt in ("bc4s", "bc5s") and mip_filter not in ("box", "normal"):
@@ -302,18 +335,16 @@ def main(argv=None):
         for flag, value in (("-resizekernel", resize_kernel), ("-resizerule", resize_rule), ("-resizewrap", resize_wrap)):
             if value is not None and not size_flags:
                 raise ValueError("%s goes with -resize, -maxsize or -pow2" % flag)
-        if size_flags and fmt in ("bc6hu", "bc6hs"):
-            raise ValueError("-resize, -maxsize, -pow2: %s is encoded from half-float images, which are not resized" % fmt)
         if resize_rule == "srgb" and fmt in ("bc4s", "bc5s"):
             raise ValueError("-resizerule srgb: %s reads the image as int8, which takes box or normal" % fmt)
         if cube and len(paths) > 2 and (len(paths) - 1) % 6 != 0:
             raise ValueError("-cube takes the 6 faces of a cube (+X -X +Y -Y +Z -Z) or 6 n of a cube array, got %d inputs" % (len(paths) - 1))
         if array or cube:
-            layers = load_layers(paths[:-1])
+            layers = load_layers(paths[:-1], fmt)
             if cube and (layers.shape[0] % 6 != 0 or layers.shape[1] != layers.shape[2]):
                 raise ValueError("-cube needs 6 n square faces, got %d of %dx%d" % (layers.shape[0], layers.shape[2], layers.shape[1]))
         else:
-            image = load_rgba8(paths[0])
+            image = load_rgba16f(paths[0], fmt) if fmt in HALF_FORMATS else load_rgba8(paths[0])
         if size_flags:
             loaded = layers if (array or cube) else image
             target = resized_size(loaded.shape[-2], loaded.shape[-3], resize, maxsize, pow2)
@@ -324,12 +355,12 @@ def main(argv=None):
         return 1
     if size_flags and target != (loaded.shape[-2], loaded.shape[-3]):
         loaded = resize_file(loaded, target[0], target[1], resize_kernel or "lanczos3", resize_rule or "box", resize_wrap or "clamp",
-                             signed=fmt in ("bc4s", "bc5s"))
+                             signed=fmt in ("bc4s", "bc5s"), hdr=HALF_FORMATS.get(fmt))
         if array or cube:
             layers = loaded
         else:
             image = loaded
-    how = dict(mip_filter=mip_filter, kernel=mip_kernel, wrap=wrap or "clamp")
+    how = dict(mip_filter=mip_filter, kernel=mip_kernel, wrap=wrap or "clamp", hdr=HALF_FORMATS.get(fmt) if mip_kernel is not None else None)
     options = api.Options()
     if uniform:  # etc2packer.cpp:202-205
         options.flags |= api.Flags.Uniform

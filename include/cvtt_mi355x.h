@@ -376,10 +376,29 @@ int cvttmi_compact_rows_device(cvttmi_context *ctx, void *d_out, const void *d_p
  *       |S_c| < 2^20: exact as a float).  All three S_c zero: the plain rule on the three channels' bytes.  Otherwise, in IEEE single
  *       precision, every operation rounded on its own: len = sqrtf((fx * fx + fy * fy) + fz * fz), q = fS_c / len, and the two
  *       re-encode formulas above applied to q.
- * With a kernel RGBA8 takes BOX, SRGB and NORMAL, RGBA8_SNORM BOX and NORMAL, under any one wrap mode.  CVTTMI_E_INVALID with an
- * error text, nothing queued, nothing written: a kernel with RGBA16F (a kernel with negative lobes rings below zero in HDR data:
- * what to do there is a decision of its own) or with ALPHA_WEIGHTED (the weighted mean's denominator can turn negative: likewise),
- * a wrap flag without a kernel, both wrap flags, an unknown kernel code.
+ * RGBA16F under a kernel.  A kernel with negative lobes rings below zero in HDR data (on a log-normal test image 28 % of the texels
+ * of a Lanczos3 level are negative before any clamp), so the caller states the range of the results with one of two flags of the
+ * filter word, CVTTMI_MIP_HDR_NONNEGATIVE: results clamped to [+0, 65504], or CVTTMI_MIP_HDR_SIGNED: to [-65504, 65504].  Valid
+ * words: a flag goes only with CVTTMI_PIXELS_RGBA16F and the rule field CVTTMI_MIP_FILTER_BOX (the plain rule); in the mip calls
+ * only together with a kernel (the 2x2 box of RGBA16F stays exactly what it is), in the resize calls with any kernel code, 0
+ * included; exactly one of the two is required.  Geometry, taps, first taps, wraps and Q14 tables are those of the RGBA8 rules.
+ * Arithmetic, per channel, all four channels alike, in IEEE binary32 round-to-nearest-even, every product and every sum rounded on
+ * its own (no fused multiply-add):
+ *       w_k = (float)q_k * 2^-14 (exact);  v = the half converted to float (exact)
+ *       horizontal: h = +0.0f;  for k = 0 .. n-1 in index order: h = h + (w_k * v_k)
+ *       vertical:   s = +0.0f;  for j in index order: s = s + (w_j * h_j)
+ *       c = s < lo ? lo : (s > 65504.0f ? 65504.0f : s), lo = +0.0f (NONNEGATIVE) or -65504.0f (SIGNED);  out = half(c), round to
+ *       nearest even, half subnormals produced, not flushed.
+ *   No binary32 subnormal can arise (every intermediate is 0 or at least 2^-52 in magnitude); the sums never hold -0, because they
+ *   start from +0; under SIGNED a small negative s converts to 0x8000, as IEEE conversion does; under NONNEGATIVE every s <= 0 gives
+ *   0x0000.  Finite inputs are the contract, as for the box: with non-finite inputs only the texels whose footprint holds one are
+ *   affected -- a NaN stays a NaN (bits unspecified), +-Inf sums are clamped like any value.  The restatement in numpy float32 is
+ *   exact (tests/hdr_resample_ref.py); a fused step would not be, since emulating it through float64 rounds twice.
+ * With a kernel RGBA8 takes BOX, SRGB and NORMAL, RGBA8_SNORM BOX and NORMAL, RGBA16F BOX with one range flag, under any one wrap
+ * mode.  CVTTMI_E_INVALID with an error text, nothing queued, nothing written: a kernel with RGBA16F and no range flag, both range
+ * flags, a range flag with RGBA8 / RGBA8_SNORM, with SRGB / NORMAL / ALPHA_WEIGHTED or without a kernel, a kernel with
+ * ALPHA_WEIGHTED (the weighted mean's denominator can turn negative: what to do there is a decision of its own), a wrap flag without
+ * a kernel, both wrap flags, an unknown kernel code, and any other bit (0x800 among them).
  * cvttmi_mip_kernel_taps: host only, no context.  Copies the table of the word's kernel to taps[0 .. 11] (zeros beyond *count = n);
  * CVTTMI_E_INVALID for kernel 0, an unknown kernel or a NULL pointer.
  * cvttmi_srgb_tables: host only, no context.  Copies T and U (U[k] at thresholds[k - 1]); CVTTMI_E_INVALID for a NULL pointer.
@@ -428,6 +447,8 @@ int cvttmi_build_mips_device(cvttmi_context *ctx, void *d_pyramid, size_t pyrami
 #define CVTTMI_MIP_KERNEL_KAISER 0x40
 #define CVTTMI_MIP_WRAP_REPEAT 0x200 /* bits 9-10: how a kernel's taps leave the image; 0 = clamp to the edge */
 #define CVTTMI_MIP_WRAP_MIRROR 0x400
+#define CVTTMI_MIP_HDR_NONNEGATIVE 0x1000 /* RGBA16F under a kernel / in a resize: results clamped to [+0, 65504] */
+#define CVTTMI_MIP_HDR_SIGNED 0x2000      /* ... clamped to [-65504, 65504]; exactly one of the two */
 int cvttmi_build_mips_filtered_device(cvttmi_context *ctx, void *d_pyramid, size_t pyramidBytes, const void *d_image, uint32_t width,
                                       uint32_t height, size_t rowPitchBytes, int pixelFormat, uint32_t levels, uint32_t filter,
                                       void *hipStream);
@@ -461,15 +482,20 @@ int cvttmi_mip_kernel_taps(uint32_t filter, int16_t taps[12], uint32_t *count);
  * with the weight row of the output column in the first pass and of the output row in the second:
  *   plain rule, and always channel 3:  h' = (h + 512) >> 10;  out = clamp((s + 2^17) >> 18, 0..255 or -128..127)
  *   CVTTMI_MIP_FILTER_SRGB and _NORMAL: word for word as stated above for kernels.
- * RGBA8 takes the plain rule, SRGB and NORMAL; RGBA8_SNORM the plain rule and NORMAL; RGBA16F and ALPHA_WEIGHTED are refused for the
- * reasons given above for kernels.
+ * RGBA8 takes the plain rule, SRGB and NORMAL; RGBA8_SNORM the plain rule and NORMAL; ALPHA_WEIGHTED is refused for the reason given
+ * above for kernels.  RGBA16F takes the plain rule with exactly one CVTTMI_MIP_HDR_* flag, under any kernel code, the box (0)
+ * included: the float arithmetic stated above under "RGBA16F under a kernel", word for word, with the weight row of the output column
+ * in the first pass and of the output row in the second, the tables, first taps and wraps of this section.  Without a flag RGBA16F is
+ * refused, and so are both flags, a flag with RGBA8 / RGBA8_SNORM and a flag with SRGB, NORMAL or ALPHA_WEIGHTED.  At exactly half
+ * the size the result is the mip kernel's level; at the same size it is the image, but for what the range clamps, -0 (which becomes
+ * +0) and NaN bits.
  * cvttmi_resize_taps: host only, no context; the one owner of the rule (the device call uses its output).  Reports *tapsPerRow = n;
  *   with weights != NULL it also fills weights[x * n + k] (dst x n values) and first[x] (dst values).  Only the kernel field of
- *   `filter` matters to the table; the word must be a valid one.  CVTTMI_E_INVALID: a size of 0 or above 65535, a word that is
- *   none, NULL tapsPerRow, weights without first, a table the guard refuses.
+ *   `filter` matters to the table; the word must be a valid one (of RGBA8, or of RGBA16F: the plain rule with one range flag).
+ *   CVTTMI_E_INVALID: a size of 0 or above 65535, a word that is none, NULL tapsPerRow, weights without first, a table the guard refuses.
  * cvttmi_resize_work_bytes: host only, no context.  *workBytes = what cvttmi_resize_image_device needs at d_work for these
  *   arguments: the tables of both axes and, where the resize takes two launches, the intermediate (layers x srcH x dstW entries
- *   of 8 bytes, 16 under SRGB and NORMAL).  cvttmi_resize_launches: *launches = 1 where the source rows under every tile of 64 x 16
+ *   of 8 bytes, 16 under SRGB and NORMAL and for RGBA16F).  cvttmi_resize_launches: *launches = 1 where the source rows under every tile of 64 x 16
  *   output texels fit in LDS (52 KB), 2 otherwise.  Both reject (CVTTMI_E_INVALID) what the device call rejects
  *   of these arguments.
  * cvttmi_resize_image_device: `layers` images of srcW x srcH at d_src (srcRowPitchBytes between rows, srcLayerPitchBytes between
@@ -478,11 +504,12 @@ int cvttmi_mip_kernel_taps(uint32_t filter, int16_t taps[12], uint32_t *count);
  *   built in page-locked memory of the context (a ring of four slots, each grown by the first call that needs more; a call with
  *   the sizes and kernel of a slot's tables does not build them again) and copied to d_work on hipStream: calls queued back to
  *   back wait for nothing but, after four later tables, the copy that read a slot.  Nothing else is allocated.  Writes exactly dstW x 4
- *   bytes of each of the dstH rows of each layer -- not the pitch gaps -- and nothing outside d_work[0, workBytes).  Source and
- *   destination must not overlap.  CVTTMI_E_INVALID with an error text before anything is queued, nothing written: NULL pointers, d_src
- *   / d_dst not on a 4-byte, d_work not on a 256-byte boundary, a size or layers of 0 or above 65535, a row pitch below the row or no
- *   multiple of 4, a layer pitch below height x row pitch or no multiple of 4, workBytes too small, a pixel kind other than RGBA8 /
- *   RGBA8_SNORM, SRGB with RGBA8_SNORM, ALPHA_WEIGHTED or any other rule, an unknown kernel code, both wrap flags, a refused table. */
+ *   (RGBA16F: dstW x 8) bytes of each of the dstH rows of each layer -- not the pitch gaps -- and nothing outside d_work[0, workBytes).
+ *   Source and destination must not overlap.  CVTTMI_E_INVALID with an error text before anything is queued, nothing written: NULL
+ *   pointers, d_src / d_dst not on a 4-byte (RGBA16F: 8-byte), d_work not on a 256-byte boundary, a size or layers of 0 or above 65535,
+ *   a row pitch below the row or no multiple of 4 (8), a layer pitch below height x row pitch or no multiple of 4 (8), workBytes too
+ *   small, an unknown pixel kind, RGBA16F without exactly one range flag, a range flag with anything but RGBA16F and the plain rule,
+ *   SRGB with RGBA8_SNORM, ALPHA_WEIGHTED or any other rule, an unknown kernel code, both wrap flags, a refused table. */
 int cvttmi_resize_taps(uint32_t src, uint32_t dst, uint32_t filter, int16_t *weights, int32_t *first, uint32_t *tapsPerRow);
 int cvttmi_resize_work_bytes(uint32_t srcW, uint32_t srcH, uint32_t dstW, uint32_t dstH, int pixelFormat, uint32_t filter, uint32_t layers,
                              size_t *workBytes);
