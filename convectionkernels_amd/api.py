@@ -1204,6 +1204,12 @@ class Context:
         esz = images.element_size()
         return images, row * esz, layer * esz
 
+    @staticmethod
+    def _pixel_kind(images, signed):
+        """the PIXELS_* kind of _images_in's tensor: float16 is RGBA16F, int8 or signed=True the int8 reading of RGBA8"""
+        import torch
+        return PIXELS_RGBA16F if images.element_size() == 2 else PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+
     def build_mips_array(self, images, levels=None, signed=False, stream=None, filter="box", kernel=None, wrap="clamp", hdr=None):
         """(L, H, W, 4) CUDA tensor (or a list of (H, W, 4) ones) -> [layer][level] images (cvttmi_build_mips_array_device): the mip
         chain of every layer, ONE launch per level for all of them.  [l][0] is a view of the input, the others are (h_L, w_L, 4) views
@@ -1215,7 +1221,7 @@ class Context:
         esz = images.element_size()
         if esz == 2 and signed:
             raise CvttError("signed selects the int8 rule of an RGBA8 image")
-        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+        kind = self._pixel_kind(images, signed)
         layout = mip_layout(w, h, 4 * esz, 16, levels)
         sizes = texture_layout(w, h, 4 * esz, 16, len(layout), n)
         pyramids = torch.empty(sizes.pyramidBytes, dtype=torch.uint8, device=images.device)
@@ -1252,7 +1258,7 @@ class Context:
         esz = images.element_size()
         n, h, w = (int(v) for v in images.shape[:3])
         width, height = _u32(width, "width"), _u32(height, "height")
-        kind = PIXELS_RGBA16F if esz == 2 else PIXELS_RGBA8_SNORM if (signed or images.dtype == torch.int8) else PIXELS_RGBA8
+        kind = self._pixel_kind(images, signed)
         word = resize_filter_word(kernel, filter, wrap, hdr)
         shape = (n, height, width, 4)
         if out is None:

@@ -34,7 +34,7 @@ hipError_t cvttmi_launch_tile_chain(const CvttTextureLevels *levels, void *d_til
 hipError_t cvttmi_launch_compact_chain(const CvttTextureLevels *levels, const void *d_packed, void *d_out, uint32_t bytesPerBlock,
                                        hipStream_t stream);
 
-// mip_kernel.hip, mip_filter_kernel.hip, mip_resample_kernel.hip, resize_kernel.hip
+// mip_filter_kernel.hip (both downsample entries), mip_resample_kernel.hip, resize_kernel.hip
 hipError_t cvttmi_launch_downsample(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch, size_t dstLayer,
                                     uint32_t srcW, uint32_t srcH, uint32_t layers, int kind, hipStream_t stream);
 hipError_t cvttmi_launch_downsample_filtered(const void *d_src, size_t srcPitch, size_t srcLayer, void *d_dst, size_t dstPitch,

@@ -1,5 +1,5 @@
-// What the mip and resize kernels share (mip_kernel.hip: the box filter; resample_common.h: every other filter): the pixel kinds,
-// the box rule on four bytes at once, and the shape of a level's launch.
+// What the mip and resize kernels share before any rule (resample_common.h includes it, and every kernel file includes that): the
+// pixel kinds, the box rule on four bytes at once, and the shape of a level's launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,6 @@
 // The mip kernels wider than 2x2 (include/cvtt_mi355x.h, "mip chains", CVTTMI_MIP_KERNEL_* and CVTTMI_MIP_WRAP_*): one level per
-// launch like the other mip filters, RGBA8 and RGBA8_SNORM texels (RGBA16F: its own kernel further down).  An output texel reads n x n source texels (n = 4, 8 or
+// launch like the other mip filters, one kernel template for every pixel kind (RGBA8 and RGBA8_SNORM described first, RGBA16F
+// at the end).  An output texel reads n x n source texels (n = 4, 8 or
 // 12 taps per direction, one Q14 table for every texel: tools/gen_mip_kernels.py), separably:
 //   a workgroup of 256 lanes owns a tile of kTileX x kTileY output texels.  Horizontal pass: for each of the 2 kTileY + n - 2
 //   source rows under the tile (wrapped), a lane makes four neighbouring h' from one window of n + 6 source texels -- 16-byte
@@ -12,6 +13,10 @@
 // 48.5 KB a workgroup: three workgroups share a CU.  The taps arrive as kernel arguments (scalar registers).  No scratch.
 // Every product is a 24-bit multiply (__mul24: full rate, where a 32-bit multiply runs at a quarter): a tap is below 2^13, a value
 // or an h' below 2^17 (sRGB: T <= 65535, |h'| <= 78727), and the generator asserts that the sums stay inside int32.
+// RGBA16F (resample_common.h, "RGBA16F"; the plain rule only): the same tile, items and lanes with KIND = kRGBA16F.  A texel is a
+// uint2, so a 16-byte read holds two; the window of n + 6 texels starts at an odd column, so one texel leads it from the 16-byte
+// boundary.  Taps, sums and entries are floats: an LDS entry is the four float sums (42 x 64 x 16 B at most, as under SRGB, and no
+// tables), an output texel an 8-byte store of the sums clamped to [lo, 65504].  No scratch.
 #include "resample_common.h"
 #include "cvtt_launchers.h"
 
@@ -23,23 +28,40 @@ enum
     kTileY = 16
 };
 
+// what the pixel kind decides: the texel, the number type of taps, sums and entries, and one multiply-add
+template <int KIND>
 struct MipTaps
 {
-    int w[12];
+    typename std::conditional<KIND == kRGBA16F, float, int>::type w[12];
 };
 
+__device__ __forceinline__ int mulAdd(int acc, int w, int v)
+{
+    return acc + __mul24(w, v);
+}
+
+__device__ __forceinline__ float mulAdd(float acc, float w, float v) // the product and the sum round on their own (-ffp-contract=off)
+{
+    return acc + w * v;
+}
+
+// `lo`: the lower clamp of an RGBA16F texel (the integer kinds do not read it)
 template <int KIND, int RULE, int NTAPS>
 __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
                                                                   uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW, uint32_t srcH,
                                                                   uint32_t dstW, uint32_t dstH, size_t srcLayer, size_t dstLayer,
-                                                                  uint32_t wrap, uint32_t wide, uint32_t tilesY, MipTaps taps)
+                                                                  uint32_t wrap, uint32_t wide, uint32_t tilesY, MipTaps<KIND> taps, float lo)
 {
+    constexpr bool kHalf = KIND == kRGBA16F;
+    typedef typename std::conditional<kHalf, uint2, uint32_t>::type Texel;
+    typedef typename std::conditional<kHalf, float, int>::type Num;
+    typedef typename std::conditional<kHalf, float4, typename std::conditional<RULE == kSrgb, int4, short4>::type>::type Entry;
+    constexpr int kPer = 16 / sizeof(Texel);      // texels of a 16-byte read
     constexpr int kRows = 2 * kTileY + NTAPS - 2; // source rows under a tile
     constexpr int kWindow = NTAPS + 6;            // source texels (LDS rows) under four neighbouring outputs
-    constexpr int kLead = (1 - NTAPS / 2) & 3;    // texels between the 16-byte boundary and the window's first texel
-    constexpr int kChunks = (kLead + kWindow + 3) / 4;
+    constexpr int kLead = (1 - NTAPS / 2) & (kPer - 1); // texels between the 16-byte boundary and the window's first texel
+    constexpr int kChunks = (kLead + kWindow + kPer - 1) / kPer;
     constexpr int kSums = RULE == kNormal ? 7 : 4;
-    typedef typename std::conditional<RULE == kSrgb, int4, short4>::type Entry;
     __shared__ Entry hbuf[kRows * kTileX];
     __shared__ short4 pbuf[RULE == kNormal ? kRows * kTileX : 1]; // NORMAL: the plain h' of channels 0..2
     __shared__ SrgbTables tables;                                 // (no LDS is allocated where it is not read)
@@ -65,57 +87,75 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
             const uint32_t r = item / groups, g = item - r * groups;
             const Walk wy = walkFrom(2 * (int64_t)y0 + 1 - NTAPS / 2 + (int64_t)r, srcH, wrap);
             const uint8_t *row = src + (size_t)walkIndex(wy) * srcPitch;
-            const int64_t c0 = 2 * (int64_t)(x0 + 4u * g) + 1 - NTAPS / 2 - kLead; // a multiple of 4
-            uint32_t texel[4 * kChunks];
+            const int64_t c0 = 2 * (int64_t)(x0 + 4u * g) + 1 - NTAPS / 2 - kLead; // a multiple of kPer
+            Texel texel[kPer * kChunks];
             Walk wx = walkFrom(c0, srcW, wrap);
 #pragma unroll
             for (int q = 0; q < kChunks; q++)
             {
-                const int64_t c = c0 + 4 * q;
-                if (wide && c >= 0 && c + 4 <= (int64_t)srcW)
+                const int64_t c = c0 + kPer * q;
+                if (wide && c >= 0 && c + kPer <= (int64_t)srcW)
                 {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * c);
-                    texel[4 * q] = v.x;
-                    texel[4 * q + 1] = v.y;
-                    texel[4 * q + 2] = v.z;
-                    texel[4 * q + 3] = v.w;
+                    const uint4 v = *reinterpret_cast<const uint4 *>(row + sizeof(Texel) * c);
+                    if constexpr (kHalf)
+                    {
+                        texel[2 * q] = make_uint2(v.x, v.y);
+                        texel[2 * q + 1] = make_uint2(v.z, v.w);
+                    }
+                    else
+                    {
+                        texel[4 * q] = v.x;
+                        texel[4 * q + 1] = v.y;
+                        texel[4 * q + 2] = v.z;
+                        texel[4 * q + 3] = v.w;
+                    }
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
+                    for (int e = 0; e < kPer; e++)
                         walkStep(wx); // (inside the row the walk is at c itself, under every wrap)
                 }
                 else
                 {
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
+                    for (int e = 0; e < kPer; e++)
                     {
-                        texel[4 * q + e] = reinterpret_cast<const uint32_t *>(row)[walkIndex(wx)];
+                        texel[kPer * q + e] = reinterpret_cast<const Texel *>(row)[walkIndex(wx)];
                         walkStep(wx);
                     }
                 }
             }
-            int h[4][kSums];
+            Num h[4][kSums];
 #pragma unroll
             for (int c = 0; c < kSums; c++)
             {
-                int v[kWindow];
+                Num v[kWindow];
 #pragma unroll
                 for (int i = 0; i < kWindow; i++)
-                    v[i] = ruleValue<KIND, RULE>(texel[kLead + i], c, tables.lin);
+                {
+                    if constexpr (kHalf)
+                        v[i] = halfValue((c < 2 ? texel[kLead + i].x : texel[kLead + i].y) >> (16 * (c & 1)));
+                    else
+                        v[i] = ruleValue<KIND, RULE>(texel[kLead + i], c, tables.lin);
+                }
 #pragma unroll
                 for (int j = 0; j < 4; j++)
                 {
-                    int acc = 0;
+                    Num acc = 0;
 #pragma unroll
                     for (int k = 0; k < NTAPS; k++)
-                        acc += __mul24(taps.w[k], v[2 * j + k]);
-                    h[j][c] = (RULE == kSrgb && c < 3) ? (acc + (1 << 13)) >> 14 : (acc + 512) >> 10;
+                        acc = mulAdd(acc, taps.w[k], v[2 * j + k]);
+                    if constexpr (kHalf)
+                        h[j][c] = acc;
+                    else
+                        h[j][c] = (RULE == kSrgb && c < 3) ? (acc + (1 << 13)) >> 14 : (acc + 512) >> 10;
                 }
             }
 #pragma unroll
             for (int j = 0; j < 4; j++)
             {
                 const uint32_t at = r * kTileX + 4u * g + j;
-                if constexpr (RULE == kSrgb)
+                if constexpr (kHalf)
+                    hbuf[at] = make_float4(h[j][0], h[j][1], h[j][2], h[j][3]);
+                else if constexpr (RULE == kSrgb)
                     hbuf[at] = make_int4(h[j][0], h[j][1], h[j][2], h[j][3]);
                 else
                     hbuf[at] = make_short4((short)h[j][0], (short)h[j][1], (short)h[j][2], (short)h[j][3]);
@@ -129,7 +169,7 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
         const uint32_t x = lane & (kTileX - 1), yg = lane / kTileX;
         if (x0 + x < dstW && 4u * yg < tileH)
         {
-            int s[4][4];
+            Num s[4][4];
 #pragma unroll
             for (int j = 0; j < 4; j++)
 #pragma unroll
@@ -139,220 +179,88 @@ __global__ void __launch_bounds__(256) cvttmi_mipresample_kernel(const uint8_t *
             for (int i = 0; i < kWindow; i++)
             {
                 const Entry e = hbuf[(8u * yg + i) * kTileX + x];
-                const int ev[4] = {e.x, e.y, e.z, e.w};
+                const Num ev[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
                 for (int j = 0; j < 4; j++)
                     if (i - 2 * j >= 0 && i - 2 * j < NTAPS)
                     {
 #pragma unroll
                         for (int c = 0; c < 4; c++)
-                            s[j][c] += __mul24(taps.w[i - 2 * j], ev[c]);
+                            s[j][c] = mulAdd(s[j][c], taps.w[i - 2 * j], ev[c]);
                     }
             }
 #pragma unroll
             for (int j = 0; j < 4; j++)
             {
-                uint32_t out = plainByte<KIND>(s[j][3]) << 24;
-                if (RULE == kPlain)
+                if constexpr (kHalf)
                 {
-#pragma unroll
-                    for (int c = 0; c < 3; c++)
-                        out |= plainByte<KIND>(s[j][c]) << (8 * c);
-                }
-                else if (RULE == kSrgb)
-                {
-#pragma unroll
-                    for (int c = 0; c < 3; c++)
-                        out |= srgbEncode(tables, static_cast<uint32_t>(min(max((s[j][c] + (1 << 11)) >> 12, 0), 4 * 65535))) << (8 * c);
+                    if (4u * yg + j < tileH)
+                        reinterpret_cast<Texel *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = rangedTexel(s[j], lo);
                 }
                 else
                 {
-                    const int S[3] = {(s[j][0] + 128) >> 8, (s[j][1] + 128) >> 8, (s[j][2] + 128) >> 8};
-                    if ((S[0] | S[1] | S[2]) == 0)
+                    uint32_t out = plainByte<KIND>(s[j][3]) << 24;
+                    if (RULE == kPlain)
                     {
-                        int p[3] = {0, 0, 0};
-#pragma unroll
-                        for (int k = 0; k < NTAPS; k++)
-                        {
-                            const short4 e = pbuf[(8u * yg + 2 * j + k) * kTileX + x];
-                            p[0] += __mul24(taps.w[k], e.x);
-                            p[1] += __mul24(taps.w[k], e.y);
-                            p[2] += __mul24(taps.w[k], e.z);
-                        }
 #pragma unroll
                         for (int c = 0; c < 3; c++)
-                            out |= plainByte<KIND>(p[c]) << (8 * c);
+                            out |= plainByte<KIND>(s[j][c]) << (8 * c);
+                    }
+                    else if (RULE == kSrgb)
+                    {
+#pragma unroll
+                        for (int c = 0; c < 3; c++)
+                            out |= srgbEncode(tables, static_cast<uint32_t>(min(max((s[j][c] + (1 << 11)) >> 12, 0), 4 * 65535))) << (8 * c);
                     }
                     else
                     {
-                        const float fx = static_cast<float>(S[0]), fy = static_cast<float>(S[1]), fz = static_cast<float>(S[2]);
-                        const float f[3] = {fx, fy, fz};
-                        const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
+                        const int S[3] = {(s[j][0] + 128) >> 8, (s[j][1] + 128) >> 8, (s[j][2] + 128) >> 8};
+                        if ((S[0] | S[1] | S[2]) == 0)
+                        {
+                            int p[3] = {0, 0, 0};
 #pragma unroll
-                        for (int c = 0; c < 3; c++)
-                            out |= normalByte<KIND>(f[c] / len) << (8 * c);
+                            for (int k = 0; k < NTAPS; k++)
+                            {
+                                const short4 e = pbuf[(8u * yg + 2 * j + k) * kTileX + x];
+                                p[0] += __mul24(taps.w[k], e.x);
+                                p[1] += __mul24(taps.w[k], e.y);
+                                p[2] += __mul24(taps.w[k], e.z);
+                            }
+#pragma unroll
+                            for (int c = 0; c < 3; c++)
+                                out |= plainByte<KIND>(p[c]) << (8 * c);
+                        }
+                        else
+                        {
+                            const float fx = static_cast<float>(S[0]), fy = static_cast<float>(S[1]), fz = static_cast<float>(S[2]);
+                            const float f[3] = {fx, fy, fz};
+                            const float len = sqrtf((fx * fx + fy * fy) + fz * fz); // (every operation rounds on its own: -ffp-contract=off)
+#pragma unroll
+                            for (int c = 0; c < 3; c++)
+                                out |= normalByte<KIND>(f[c] / len) << (8 * c);
+                        }
                     }
+                    if (4u * yg + j < tileH)
+                        reinterpret_cast<Texel *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = out;
                 }
-                if (4u * yg + j < tileH)
-                    reinterpret_cast<uint32_t *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = out;
             }
         }
         __syncthreads(); // the next tile's horizontal pass rewrites the entries
     }
 }
 
-// RGBA16F (resample_common.h, "RGBA16F"): the same tile, items and lanes.  The window of n + 6 texels starts at an odd column, so
-// one texel leads it from the 16-byte boundary and a 16-byte read holds two texels; an LDS entry is the four float sums (42 x 64 x
-// 16 B at most, as under SRGB, and no tables), an output texel an 8-byte store.  No scratch.
-struct MipTapsF
-{
-    float w[12];
-};
-
-template <int NTAPS>
-__global__ void __launch_bounds__(256) cvttmi_mipresample_half_kernel(const uint8_t *__restrict__ src, size_t srcPitch,
-                                                                       uint8_t *__restrict__ dst, size_t dstPitch, uint32_t srcW,
-                                                                       uint32_t srcH, uint32_t dstW, uint32_t dstH, size_t srcLayer,
-                                                                       size_t dstLayer, uint32_t wrap, uint32_t wide, uint32_t tilesY,
-                                                                       MipTapsF taps, float lo)
-{
-    constexpr int kRows = 2 * kTileY + NTAPS - 2;
-    constexpr int kWindow = NTAPS + 6;
-    constexpr int kLead = (1 - NTAPS / 2) & 1; // texels between the 16-byte boundary and the window's first texel
-    constexpr int kPairs = (kLead + kWindow + 1) / 2;
-    __shared__ float4 hbuf[kRows * kTileX];
-    src += blockIdx.z * srcLayer;
-    dst += blockIdx.z * dstLayer;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t x0 = blockIdx.x * kTileX;
-    const uint32_t groups = (min(dstW - x0, (uint32_t)kTileX) + 3u) / 4u;
-    for (uint32_t ty = blockIdx.y; ty < tilesY; ty += gridDim.y)
-    {
-        const uint32_t y0 = ty * kTileY;
-        const uint32_t tileH = min(dstH - y0, (uint32_t)kTileY);
-        const uint32_t rows = 2u * tileH + NTAPS - 2u;
-
-        // horizontal pass: item = (source row r of the tile, group g of four output columns)
-        for (uint32_t item = lane; item < rows * groups; item += 256u)
-        {
-            const uint32_t r = item / groups, g = item - r * groups;
-            const Walk wy = walkFrom(2 * (int64_t)y0 + 1 - NTAPS / 2 + (int64_t)r, srcH, wrap);
-            const uint8_t *row = src + (size_t)walkIndex(wy) * srcPitch;
-            const int64_t c0 = 2 * (int64_t)(x0 + 4u * g) + 1 - NTAPS / 2 - kLead; // even
-            uint2 texel[2 * kPairs];
-            Walk wx = walkFrom(c0, srcW, wrap);
-#pragma unroll
-            for (int q = 0; q < kPairs; q++)
-            {
-                const int64_t c = c0 + 2 * q;
-                if (wide && c >= 0 && c + 2 <= (int64_t)srcW)
-                {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(row + 8 * c);
-                    texel[2 * q] = make_uint2(v.x, v.y);
-                    texel[2 * q + 1] = make_uint2(v.z, v.w);
-                    walkStep(wx); // (inside the row the walk is at c itself, under every wrap)
-                    walkStep(wx);
-                }
-                else
-                {
-#pragma unroll
-                    for (int e = 0; e < 2; e++)
-                    {
-                        texel[2 * q + e] = reinterpret_cast<const uint2 *>(row)[walkIndex(wx)];
-                        walkStep(wx);
-                    }
-                }
-            }
-            float h[4][4];
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-            {
-                float v[kWindow];
-#pragma unroll
-                for (int i = 0; i < kWindow; i++)
-                    v[i] = halfValue((c < 2 ? texel[kLead + i].x : texel[kLead + i].y) >> (16 * (c & 1)));
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < NTAPS; k++)
-                        acc = acc + taps.w[k] * v[2 * j + k];
-                    h[j][c] = acc;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                hbuf[r * kTileX + 4u * g + j] = make_float4(h[j][0], h[j][1], h[j][2], h[j][3]);
-        }
-        __syncthreads();
-
-        // vertical pass: lane = (column x of the tile, rows 4 yg .. 4 yg + 3 of the tile)
-        const uint32_t x = lane & (kTileX - 1), yg = lane / kTileX;
-        if (x0 + x < dstW && 4u * yg < tileH)
-        {
-            float s[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                    s[j][c] = 0.0f;
-#pragma unroll
-            for (int i = 0; i < kWindow; i++)
-            {
-                const float4 e = hbuf[(8u * yg + i) * kTileX + x];
-                const float ev[4] = {e.x, e.y, e.z, e.w};
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (i - 2 * j >= 0 && i - 2 * j < NTAPS)
-                    {
-#pragma unroll
-                        for (int c = 0; c < 4; c++)
-                            s[j][c] = s[j][c] + taps.w[i - 2 * j] * ev[c];
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (4u * yg + j < tileH)
-                    reinterpret_cast<uint2 *>(dst + (size_t)(y0 + 4u * yg + j) * dstPitch)[x0 + x] = rangedTexel(s[j], lo);
-        }
-        __syncthreads(); // the next tile's horizontal pass rewrites the entries
-    }
-}
-
-template <int NTAPS>
-hipError_t launchResampleHalf(const MipLayers &m, uint32_t wrap, const MipTapsF &taps, float lo, hipStream_t stream)
-{
-    const uint32_t dstW = m.srcW > 1u ? m.srcW >> 1 : 1u, dstH = m.srcH > 1u ? m.srcH >> 1 : 1u;
-    uintptr_t bits = reinterpret_cast<uintptr_t>(m.src) | m.srcPitch; // 16-byte reads: as below
-    if (m.layers > 1u)
-        bits |= m.srcLayer;
-    const uint32_t wide = (bits & 15u) == 0 ? 1u : 0u;
-    const uint32_t tilesY = (dstH + kTileY - 1u) / kTileY;
-    const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers);
-    hipLaunchKernelGGL((cvttmi_mipresample_half_kernel<NTAPS>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
-                       (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, taps, lo);
-    return hipGetLastError();
-}
-
-hipError_t resampleHalfByTaps(const MipLayers &m, uint32_t wrap, const int16_t *taps, uint32_t count, uint32_t range, hipStream_t stream)
-{
-    MipTapsF t;
-    for (uint32_t k = 0; k < 12u; k++)
-        t.w[k] = k < count ? static_cast<float>(taps[k]) * (1.0f / 16384.0f) : 0.0f;
-    const float lo = hdrRangeLow(range);
-    switch (count)
-    {
-    case 4: return launchResampleHalf<4>(m, wrap, t, lo, stream);
-    case 8: return launchResampleHalf<8>(m, wrap, t, lo, stream);
-    case 12: return launchResampleHalf<12>(m, wrap, t, lo, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
+// the taps of the kind from the Q14 table: the integers themselves, or (float)q * 2^-14 (exact)
 template <int KIND, int RULE, int NTAPS>
-hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps, hipStream_t stream)
+hipError_t launchResample(const MipLayers &m, uint32_t wrap, const int16_t *taps, uint32_t range, hipStream_t stream)
 {
+    MipTaps<KIND> t;
+    for (int k = 0; k < 12; k++)
+    {
+        if constexpr (KIND == kRGBA16F)
+            t.w[k] = k < NTAPS ? static_cast<float>(taps[k]) * (1.0f / 16384.0f) : 0.0f;
+        else
+            t.w[k] = k < NTAPS ? taps[k] : 0;
+    }
     const uint32_t dstW = m.srcW > 1u ? m.srcW >> 1 : 1u, dstH = m.srcH > 1u ? m.srcH >> 1 : 1u;
     // 16-byte reads: the first row and the pitch (and, for layers, the layer stride) on 16-byte boundaries -- the test of mipLaunchShape on
     // the source alone; the output is written a texel at a time
@@ -363,39 +271,27 @@ hipError_t launchResample(const MipLayers &m, uint32_t wrap, const MipTaps &taps
     const uint32_t tilesY = (dstH + kTileY - 1u) / kTileY;
     const dim3 grid((dstW + kTileX - 1u) / kTileX, tilesY < 65535u ? tilesY : 65535u, m.layers);
     hipLaunchKernelGGL((cvttmi_mipresample_kernel<KIND, RULE, NTAPS>), grid, dim3(256), 0, stream, (const uint8_t *)m.src, m.srcPitch,
-                       (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, taps);
+                       (uint8_t *)m.dst, m.dstPitch, m.srcW, m.srcH, dstW, dstH, m.srcLayer, m.dstLayer, wrap, wide, tilesY, t,
+                       hdrRangeLow(range));
     return hipGetLastError();
 }
 
-template <int KIND, int RULE>
-hipError_t resampleByTaps(const MipLayers &m, uint32_t wrap, const MipTaps &taps, uint32_t count, hipStream_t stream)
-{
-    switch (count)
-    {
-    case 4: return launchResample<KIND, RULE, 4>(m, wrap, taps, stream);
-    case 8: return launchResample<KIND, RULE, 8>(m, wrap, taps, stream);
-    case 12: return launchResample<KIND, RULE, 12>(m, wrap, taps, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 // the pairs of withKindRule; anything else is hipErrorInvalidValue
-// (a range goes with RGBA16F and with nothing else)
 hipError_t resampleByKind(const MipLayers &m, int kind, uint32_t rule, uint32_t wrap, uint32_t range, const int16_t *taps, uint32_t count,
                           hipStream_t stream)
 {
     if (m.srcW == 0 || m.srcH == 0)
         return hipSuccess;
-    if (!taps || count > 12u || !wrapOk(wrap) || (kind == kRGBA16F ? !hdrRangeOk(range) : range != 0))
+    if (!taps || count > 12u || !wrapOk(wrap) || !rangeFitsKind(kind, range))
         return hipErrorInvalidValue;
-    MipTaps t;
-    for (uint32_t k = 0; k < 12u; k++)
-        t.w[k] = k < count ? taps[k] : 0;
     return withKindRule(kind, rule, [&](auto k, auto r) {
-        if constexpr (k() == kRGBA16F)
-            return resampleHalfByTaps(m, wrap, taps, count, range, stream);
-        else
-            return resampleByTaps<k(), r()>(m, wrap, t, count, stream);
+        switch (count)
+        {
+        case 4: return launchResample<k(), r(), 4>(m, wrap, taps, range, stream);
+        case 8: return launchResample<k(), r(), 8>(m, wrap, taps, range, stream);
+        case 12: return launchResample<k(), r(), 12>(m, wrap, taps, range, stream);
+        default: return hipErrorInvalidValue;
+        }
     });
 }
 } // namespace

@@ -1,7 +1,7 @@
-// What the resampling kernels share (mip_filter_kernel.hip: the 2x2 filters beyond the box; mip_resample_kernel.hip: the mip kernels
-// wider than 2x2; resize_kernel.hip: any size): the rules and wraps of include/cvtt_mi355x.h's filter word, the value a texel's
-// channel contributes under a rule and the byte a rule's sum or quotient becomes, the sRGB tables in LDS, the walk along a wrapped
-// axis, and the one list of the (pixel kind, rule) pairs that exist.  mip_kernel.hip (the box) needs none of it.
+// What the resampling kernels share (mip_filter_kernel.hip: the 2x2 filters, the box among them; mip_resample_kernel.hip: the mip
+// kernels wider than 2x2; resize_kernel.hip: any size): the rules and wraps of include/cvtt_mi355x.h's filter word, the value a
+// texel's channel contributes under a rule and the byte a rule's sum or quotient becomes, the sRGB tables in LDS, the walk along a
+// wrapped axis, and the one list of the (pixel kind, rule) pairs that exist.  Every mip and resize kernel file includes it.
 #pragma once
 #include "mip_common.h"
 #include "../../include/cvtt_mi355x.h"
@@ -34,7 +34,8 @@ inline bool wrapOk(uint32_t wrap) // clamp or one flag
 // ---- the (pixel kind, rule) pairs that exist ----
 // f(kind, rule), both std::integral_constant, for the pair a call names; hipErrorInvalidValue where there is no such pair.  Under
 // a kernel and in a resize RGBA8 takes the plain rule, SRGB and NORMAL, RGBA8_SNORM the plain rule and NORMAL, RGBA16F the plain
-// rule (in float, with a range: "RGBA16F" below; its kernels are templates of their own, so f branches on the kind).
+// rule (in float, with a range: "RGBA16F" below; the kind is a parameter of the same kernel templates).  This is the only place
+// that lists the pairs: cvttmi_resize_entry_bytes answers "is there such a pair" for the host through it.
 template <class F>
 hipError_t withKindRule(int kind, uint32_t rule, F f)
 {
@@ -55,8 +56,7 @@ hipError_t withKindRule(int kind, uint32_t rule, F f)
     return hipErrorInvalidValue;
 }
 
-// The 2x2 filters: the same pairs without the plain rule (the box is mip_kernel.hip's), and ALPHA_WEIGHTED on the BOX and SRGB of
-// RGBA8.  f(kind, filter).
+// The 2x2 filters: the same pairs (the plain rule is the box), and ALPHA_WEIGHTED on the BOX and SRGB of RGBA8.  f(kind, filter).
 template <class F>
 hipError_t withKindFilter(int kind, uint32_t filter, F f)
 {
@@ -65,14 +65,7 @@ hipError_t withKindFilter(int kind, uint32_t filter, F f)
         return f(U8(), std::integral_constant<int, kAlphaWeighted>());
     if (kind == kRGBA8 && filter == (kSrgb | kAlphaWeighted))
         return f(U8(), std::integral_constant<int, kSrgb | kAlphaWeighted>());
-    if (filter == kPlain)
-        return hipErrorInvalidValue;
-    return withKindRule(kind, filter, [&](auto k, auto r) {
-        if constexpr (r() == kPlain)
-            return hipErrorInvalidValue;
-        else
-            return f(k, r);
-    });
+    return withKindRule(kind, filter, f);
 }
 
 // ---- the sRGB tables in LDS (tools/gen_srgb_tables.py) ----
@@ -206,11 +199,11 @@ __device__ __forceinline__ uint32_t normalByte(float q)
 // ---- RGBA16F: the plain rule in binary32, with a range (CVTTMI_MIP_HDR_*) ----
 // A texel is a uint2 of four halfs; a sum starts from +0 and takes its taps in index order, s = s + (w * v), the product and the sum
 // rounded on their own (-ffp-contract=off), w = (float)q * 2^-14 and the half as a float both exact.  An entry between the two
-// passes is the four sums, 16 bytes.  These kernels are templates of their own next to the integer ones, whose code they leave
-// as it is.
-inline bool hdrRangeOk(uint32_t range)
+// passes is the four sums, 16 bytes.  The kernels are the integer ones' templates with KIND = kRGBA16F: the kind chooses the texel,
+// the number type and the finish under `if constexpr`, and the integer instances' code is what it was.
+inline bool rangeFitsKind(int kind, uint32_t range) // exactly one flag with RGBA16F, none with any other kind
 {
-    return range == kHdrNonnegative || range == kHdrSigned;
+    return kind == kRGBA16F ? range == kHdrNonnegative || range == kHdrSigned : range == 0;
 }
 
 inline float hdrRangeLow(uint32_t range) // the lower clamp; the upper one is 65504 under both

@@ -36,16 +36,12 @@ namespace
         return wrap != (CVTTMI_MIP_WRAP_REPEAT | CVTTMI_MIP_WRAP_MIRROR);
     }
     // does the pixel kind take the rule and the range under a kernel (in a mip chain or a resize)?  No ALPHA_WEIGHTED there; RGBA16F
-    // takes the plain rule with exactly one range flag, and a range flag goes with nothing else.
+    // takes the plain rule with exactly one range flag, and a range flag goes with nothing else.  The (kind, rule) pairs that exist
+    // are the kernels' list (resample_common.h, withKindRule): a pair has an entry size, anything else 0.
     bool kernelRuleFits(int pixelFormat, uint32_t rule, uint32_t range)
     {
-        if (pixelFormat == CVTTMI_PIXELS_RGBA16F)
-            return rule == CVTTMI_MIP_FILTER_BOX && (range == CVTTMI_MIP_HDR_NONNEGATIVE || range == CVTTMI_MIP_HDR_SIGNED);
-        if (range != 0)
-            return false;
-        if (pixelFormat == CVTTMI_PIXELS_RGBA8)
-            return rule == CVTTMI_MIP_FILTER_BOX || rule == CVTTMI_MIP_FILTER_SRGB || rule == CVTTMI_MIP_FILTER_NORMAL;
-        return pixelFormat == CVTTMI_PIXELS_RGBA8_SNORM && (rule == CVTTMI_MIP_FILTER_BOX || rule == CVTTMI_MIP_FILTER_NORMAL);
+        const bool oneFlag = range == CVTTMI_MIP_HDR_NONNEGATIVE || range == CVTTMI_MIP_HDR_SIGNED;
+        return cvttmi_resize_entry_bytes(pixelFormat, rule) != 0 && (pixelFormat == CVTTMI_PIXELS_RGBA16F ? oneFlag : range == 0);
     }
     // the tap table of a mip kernel and its length; NULL for kernel 0 and unknown kernels
     const int16_t *mipKernelTaps(uint32_t code, uint32_t *count)
@@ -203,7 +199,7 @@ extern "C"
                          uint32_t filter, hipStream_t stream)
     {
         const uint32_t kGridLayers = 65535; // the z limit of a grid
-        // a kernel's table with the rule and the wrap, else the box, else a 2x2 filter (mipFilterFits has passed the word)
+        // a kernel's table with the rule and the wrap, else a 2x2 filter, the box among them (mipFilterFits has passed the word)
         const FilterWord f = splitFilter(filter);
         uint32_t tapCount = 0;
         const int16_t *taps = mipKernelTaps(f.code, &tapCount);
@@ -218,11 +214,8 @@ extern "C"
                 const hipError_t e =
                     taps ? cvttmi_launch_resample(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes, table[l - 1].width,
                                                   table[l - 1].height, n, pixelFormat, f.rule, f.wrap, f.range, taps, tapCount, stream)
-                    : f.rule == CVTTMI_MIP_FILTER_BOX
-                        ? cvttmi_launch_downsample(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes, table[l - 1].width,
-                                                   table[l - 1].height, n, pixelFormat, stream)
-                        : cvttmi_launch_downsample_filtered(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes,
-                                                            table[l - 1].width, table[l - 1].height, n, pixelFormat, f.rule, stream);
+                         : cvttmi_launch_downsample_filtered(src, srcPitch, srcLayer, dst, table[l].rowPitchBytes, pyramidLayerBytes,
+                                                             table[l - 1].width, table[l - 1].height, n, pixelFormat, f.rule, stream);
                 if (e != hipSuccess)
                     return fail(ctx, CVTTMI_E_HIP, "downsample kernel launch", e);
                 src = dst;

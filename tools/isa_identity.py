@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Are the kernels of two builds of the library the same instructions?  (developer tool, no GPU needed)
-   python tools/isa_identity.py [--rename REGEX=TEXT] [--gone REGEX] parent/libcvtt_mi355x.so [lib.so]
+   python tools/isa_identity.py [--rename REGEX=TEXT]... [--gone REGEX] parent/libcvtt_mi355x.so [lib.so]
 Disassembles the gfx950 code objects of both libraries (kernel_resources.code_objects, llvm-objdump -d) and compares kernel
 by kernel: the instruction stream without addresses, and the register / LDS / scratch figures of the metadata.  For a kernel
 that differs it prints the instruction counts and the histogram of mnemonics that changed.  Exit status 1 if any differs.
---rename: the first library's kernel names are compared under re.sub(REGEX, TEXT), for a change that only renames kernels.
+--rename: the first library's kernel names are compared under re.sub(REGEX, TEXT), for a change that only renames kernels; given
+more than once, the maps are applied in the order given.
 --gone: kernels of the first library that the change removes on purpose; they are listed and do not count as differing.  Both
 are searched in every kernel's name, so they name the kernels they mean: dropping a trailing `true` of the mip kernels alone is
    --rename '^(cvttmi_(?:downsample|mipfilter|mipresample)\w*<.*), true>$=\1>' --gone '^cvttmi_(downsample|mipfilter|mipresample)\w*<.*, false>$'
@@ -78,10 +79,10 @@ def source_sha256(path):
 
 def main():
     args = sys.argv[1:]
-    rename, gone = None, None
+    renames, gone = [], None
     while args and args[0] in ("--rename", "--gone"):
         if args[0] == "--rename":
-            rename = args[1].split("=", 1)
+            renames.append(args[1].split("=", 1))
         else:
             gone = args[1]
         args = args[2:]
@@ -95,9 +96,9 @@ def main():
     if gone:
         for k in sorted(k for k in A if re.search(gone, k)):
             print("%-72s %6d instructions  gone (only in the first, as stated)" % (k[:72], len(A.pop(k))))
-    if rename:
-        A = {re.sub(rename[0], rename[1], k): v for k, v in A.items()}
-        RA = {re.sub(rename[0], rename[1], k): v for k, v in RA.items()}
+    for regex, text in renames:
+        A = {re.sub(regex, text, k): v for k, v in A.items()}
+        RA = {re.sub(regex, text, k): v for k, v in RA.items()}
     differing = 0
     for k in sorted(set(A) | set(B)):
         if k not in A or k not in B:
